@@ -12,9 +12,15 @@ the timed region is pure steady-state serving; p50 queue-wait (submit ->
 first token) is measured during warmup and reported in config.
 
 Launch (driver):
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set up, warm up, time the K
+steps, print the result line.  --dump-outputs DIR additionally writes what
+the last timed step computed (see dump_outputs) so two builds can be compared
+output for output; --full is where any extra measurement beyond the headline
+belongs (none today: --stack is its own mode with its own result line).
 
 The reference publishes no number for this metric =>
 vs_baseline is null.
@@ -167,6 +173,44 @@ def run_stack(args):
         node.wait(timeout=30)
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(dirname, eng, users, steps):
+    """Write what the timed path produced as DIR/<name>.npy (float32/64).
+
+    tokens  [users, steps] float64 - the token ids every user received from
+            the timed steps, in submission order (last column = last step)
+    logits  [users, vocab] float32 - the last timed step's logits, when the
+            engine still holds them (graphed GPU decode keeps them in the
+            graph's static output buffer)
+    An array that would push the total past 64 MB is replaced by a fixed,
+    seeded sample of its flattened elements."""
+    import numpy as np
+
+    eng._drain_pipe()   # the pipelined host runs one token behind the GPU
+    seqs = sorted(eng.running, key=lambda s: s.seq_id)
+    arrays = {"tokens": np.asarray([s.generated[-steps:] for s in seqs],
+                                   dtype=np.float64)}
+    entry = eng._graphs.get((eng._bucket(users), eng._samp_class(seqs))) \
+        if eng.use_graphs else None
+    if entry is not None and entry["logits"] is not None:
+        # graph rows follow eng.running order; re-order to submission order
+        row = {s.seq_id: i for i, s in enumerate(eng.running)}
+        idx = torch.tensor([row[s.seq_id] for s in seqs],
+                           device=entry["logits"].device)
+        arrays["logits"] = entry["logits"][idx].float().cpu().numpy()
+
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, a in arrays.items():
+        if a.nbytes > left:
+            keep = np.random.default_rng(0).permutation(a.size)
+            a = a.reshape(-1)[np.sort(keep[:left // a.itemsize])]
+        left -= a.nbytes
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -182,6 +226,12 @@ def main():
                     help="benchmark through the full dispatcher stack "
                          "(HTTP + scheduler + UDS workers) instead of "
                          "the engine-only kernel metric")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's "
+                         "outputs as DIR/<name>.npy (engine mode, rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements a plain run leaves out "
+                         "(none beyond the headline today)")
     args = ap.parse_args()
 
     if args.stack:
@@ -304,6 +354,8 @@ def main():
                 "load_s": round(load_s, 1),
             },
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, eng, users, args.steps)
         print(json.dumps(out), flush=True)
     if dist:
         torch.distributed.destroy_process_group()

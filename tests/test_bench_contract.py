@@ -37,6 +37,38 @@ def test_bench_single_process_defaults():
     assert out["vs_baseline"] is None
 
 
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the timed steps' tokens as float .npy, the
+    same from run to run (seeded inputs), and --full keeps the headline
+    result line intact."""
+    import numpy as np
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        r = subprocess.run(
+            [sys.executable, BENCH, "--gpus", "1", "--steps", "3",
+             "--warmup", "1", "--dump-outputs", str(d)] + extra,
+            cwd=REPO, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = last_json_line(r.stdout)
+        for k in REQUIRED:
+            assert k in out, f"missing field {k}"
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+        files = sorted(p.name for p in d.iterdir())
+        assert "tokens.npy" in files
+        assert all(f.endswith(".npy") for f in files), files
+        arrs = {f[:-4]: np.load(d / f) for f in files}
+        for a in arrs.values():
+            assert a.dtype in (np.float32, np.float64)
+        assert sum(a.nbytes for a in arrs.values()) <= 64 * 2 ** 20
+        users = out["config"]["users_per_gpu"]
+        assert arrs["tokens"].shape == (users, 3)
+        dumps.append(arrs)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
+
+
 def test_bench_torchrun_two_ranks():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))

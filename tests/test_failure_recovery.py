@@ -46,11 +46,11 @@ def _online(base):
         return None
 
 
-def test_worker_death_and_rejoin(tmp_path):
+def test_worker_death_and_rejoin(tmp_path, sock_dir):
     if not os.path.exists(BIN):
         subprocess.run([sys.executable, "-m", "ollamamq_amd.build"],
                        check=True)
-    sock = os.path.join(str(tmp_path), "w.sock")
+    sock = os.path.join(sock_dir, "w.sock")
     worker = _spawn_worker(sock)
     assert _wait_socket(sock)
     server = subprocess.Popen(
@@ -110,7 +110,7 @@ def test_worker_death_and_rejoin(tmp_path):
         worker.terminate()
 
 
-def test_midstream_worker_death_truncates_cleanly(tmp_path):
+def test_midstream_worker_death_truncates_cleanly(tmp_path, sock_dir):
     """Worker dies while a response is STREAMING: the client's stream
     ends (truncated, no done marker), the dispatcher survives, and the
     health loop flips the backend offline (SURVEY §5 mid-stream
@@ -118,7 +118,7 @@ def test_midstream_worker_death_truncates_cleanly(tmp_path):
     if not os.path.exists(BIN):
         subprocess.run([sys.executable, "-m", "ollamamq_amd.build"],
                        check=True)
-    sock = os.path.join(str(tmp_path), "w.sock")
+    sock = os.path.join(sock_dir, "w.sock")
     worker = _spawn_worker(sock)
     assert _wait_socket(sock)
     server = subprocess.Popen(

@@ -32,14 +32,14 @@ def _wait_socket(path, timeout=60):
 
 
 @pytest.fixture(scope="module")
-def node(tmp_path_factory):
+def node(tmp_path_factory, sock_dir_module):
     if not os.path.exists(BIN):
         subprocess.run([sys.executable, "-m", "ollamamq_amd.build"],
                        check=True)
     tmp = tmp_path_factory.mktemp("node")
     socks, workers = [], []
     for i in range(2):
-        sock = os.path.join(str(tmp), f"w{i}.sock")
+        sock = os.path.join(sock_dir_module, f"w{i}.sock")
         socks.append(sock)
         workers.append(subprocess.Popen(
             [sys.executable, "-m", "ollamamq_amd.engine.worker",
@@ -101,7 +101,7 @@ def test_load_spreads_across_workers(node):
 
 # --------------------------------------------------------------- config 5
 @pytest.fixture(scope="module")
-def hetero_node(tmp_path_factory):
+def hetero_node(tmp_path_factory, sock_dir_module):
     """Mixed-fleet rehearsal (BASELINE.json config 5 on CPU): two workers
     carrying ONLY tiny + one carrying ONLY tiny-qwen; requests must route
     by model (reference src/dispatcher.rs:599-620) and fair-share across
@@ -110,7 +110,7 @@ def hetero_node(tmp_path_factory):
     spec = [("tiny",), ("tiny",), ("nano",)]
     socks, workers = [], []
     for i, (model,) in enumerate(spec):
-        sock = os.path.join(str(tmp), f"h{i}.sock")
+        sock = os.path.join(sock_dir_module, f"h{i}.sock")
         socks.append(sock)
         workers.append(subprocess.Popen(
             [sys.executable, "-m", "ollamamq_amd.engine.worker",

@@ -55,9 +55,9 @@ def _wait_loaded(base, model, timeout=30):
     return False
 
 
-def test_dispatcher_restart_resumes(tmp_path):
+def test_dispatcher_restart_resumes(tmp_path, sock_dir):
     tmp = str(tmp_path)
-    sock = os.path.join(tmp, "w.sock")
+    sock = os.path.join(sock_dir, "w.sock")
     worker = subprocess.Popen(
         [sys.executable, "-m", "ollamamq_amd.engine.worker",
          "--socket", sock, "--model", "tiny-cpu", "--max-ctx", "256",

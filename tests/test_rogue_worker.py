@@ -87,11 +87,11 @@ class SlowStreamWorker(socketserver.ThreadingUnixStreamServer):
                 self.wfile.write(b'{"response": "b", "done": true}\n')
 
 
-def test_stream_survives_long_token_gap(tmp_path):
+def test_stream_survives_long_token_gap(tmp_path, sock_dir):
     """A >5 s pause between stream chunks must not truncate the response:
     the stream phase runs under the request timeout (-t), not the 5 s
     connect timeout."""
-    sock = os.path.join(str(tmp_path), "slow.sock")
+    sock = os.path.join(sock_dir, "slow.sock")
     sw = SlowStreamWorker(sock)
     t = threading.Thread(target=sw.serve_forever, daemon=True)
     t.start()
@@ -125,8 +125,8 @@ def test_stream_survives_long_token_gap(tmp_path):
 
 
 @pytest.fixture
-def rogue(tmp_path):
-    sock = os.path.join(str(tmp_path), "rogue.sock")
+def rogue(tmp_path, sock_dir):
+    sock = os.path.join(sock_dir, "rogue.sock")
     rw = RogueWorker(sock)
     t = threading.Thread(target=rw.serve_forever, daemon=True)
     t.start()

@@ -31,12 +31,12 @@ def _wait_socket(path, timeout=60):
 
 
 @pytest.fixture(scope="module")
-def stack(tmp_path_factory):
+def stack(tmp_path_factory, sock_dir_module):
     if not os.path.exists(BIN):
         subprocess.run([sys.executable, "-m", "ollamamq_amd.build"],
                        check=True)
     tmp = tmp_path_factory.mktemp("stack")
-    sock = os.path.join(str(tmp), "w0.sock")
+    sock = os.path.join(sock_dir_module, "w0.sock")
     worker = subprocess.Popen(
         [sys.executable, "-m", "ollamamq_amd.engine.worker",
          "--socket", sock, "--model", "tiny-cpu", "--max-ctx", "256",

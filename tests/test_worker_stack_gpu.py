@@ -34,10 +34,10 @@ def _wait_socket(path, timeout=120):
 
 
 @pytest.fixture(scope="module")
-def gpu_stack(tmp_path_factory):
+def gpu_stack(tmp_path_factory, sock_dir_module):
     assert os.path.exists(BIN), "native server not built"
     tmp = tmp_path_factory.mktemp("gstack")
-    sock = os.path.join(str(tmp), "wg.sock")
+    sock = os.path.join(sock_dir_module, "wg.sock")
     worker = subprocess.Popen(
         [sys.executable, "-m", "ollamamq_amd.engine.worker",
          "--socket", sock, "--gpu", "0", "--model", "tiny",
