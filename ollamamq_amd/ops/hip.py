@@ -520,6 +520,10 @@ def linear_qkv_rope(x, packed, N, bias_rp, cache, layer, positions,
     if K is None:
         M, K = x.shape
         xs, xf = x.stride(0), 0
+        if M > 32:
+            raise ValueError("linear_qkv_rope: standard-layout x supports "
+                             "M <= 32; rows 33..64 need the frag input "
+                             "(K=, M_real=)")
     else:
         M, xs, xf = M_real, 0, 1
     y = torch.empty((M, N), dtype=x.dtype, device=x.device)
@@ -590,7 +594,10 @@ def linear_packed(x, packed, bias, N, ks=None, depth=None, xlds=None,
     apply rmsnorm scaling of the raw-residual input x (norm weight must
     be folded into the pack); `res` adds the residual stream into the
     output (pass y=res for the in-place residual update) and `sq_out`
-    emits per-tile sum-of-squares partials for the next GEMM."""
+    emits per-tile sum-of-squares partials for the next GEMM.
+    Raises ValueError for combinations the kernels do not implement:
+    bias with ks > 1 and res/sq_out, sq_out without res at ks == 1, and
+    yfrag with ks > 1 without res/sq_out."""
     if K is None:
         M, K = x.shape
         xs = x.stride(0)
@@ -608,6 +615,19 @@ def linear_packed(x, packed, bias, N, ks=None, depth=None, xlds=None,
             ks = int(_WS_KS) if _WS_KS else _wstream_ksplit(N, K)
     if rstd is not None:
         ks = 1            # rstd fusion requires ks == 1
+    # argument combinations the kernels would answer wrongly, rejected
+    # before anything launches
+    fused = res is not None or sq_out is not None
+    if ks > 1 and fused and bias is not None:
+        raise ValueError("linear_packed: bias is not supported with ks > 1 "
+                         "and res/sq_out (the tile combine has no bias)")
+    if ks > 1 and yfrag and not fused:
+        raise ValueError("linear_packed: yfrag with ks > 1 needs res or "
+                         "sq_out (the plain combine writes standard layout)")
+    if ks == 1 and sq_out is not None and res is None:
+        raise ValueError("linear_packed: sq_out with ks == 1 needs res "
+                         "(partials are only accumulated in the residual "
+                         "epilogue)")
     part = ctypes.c_void_p(0)
     if ks > 1:
         key = ("ws", M, N, ks, str(x.device))

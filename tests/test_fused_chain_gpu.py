@@ -114,6 +114,70 @@ def test_fused_chain_logits_close():
     assert torch.equal(lf.argmax(-1), lg.argmax(-1))
 
 
+@pytest.mark.parametrize("B", [33, 64])
+def test_fused_chain_mt2_single_forward_rows(B):
+    """One decode forward over both 32-row frag halves, fused vs generic,
+    checked row by row: a systematically wrong row in the second half
+    cannot hide behind sequences that are allowed to diverge."""
+    from ollamamq_amd.ops.interface import AttnMeta
+    cfg, model, kv = _mk(batch=B)
+    dev = "cuda:0"
+    g = torch.Generator().manual_seed(11)
+    slots = []
+    for s in range(B):
+        slot = kv.alloc_slot()
+        slots.append(slot)
+        L = 6 + s % 9
+        kv.ensure(slot, L)
+        toks = torch.randint(0, cfg.vocab, (L,), generator=g,
+                             dtype=torch.int32).to(dev)
+        pos = torch.arange(L, dtype=torch.int32, device=dev)
+        st = torch.full((L,), slot, dtype=torch.int32, device=dev)
+        one = torch.tensor([slot], dtype=torch.int32, device=dev)
+        meta = AttnMeta(mode="prefill", slot_ids=one,
+                        seq_lens=torch.tensor([L], dtype=torch.int32,
+                                              device=dev),
+                        cu_q=torch.tensor([0, L], dtype=torch.int32,
+                                          device=dev),
+                        logits_idx=torch.tensor([L - 1], dtype=torch.long,
+                                                device=dev),
+                        max_q=L, max_kv=L, window=0)
+        model.fused_chain = False
+        model.forward(toks, pos, kv, st, meta)
+    lens = [kv.seq_lens[s] + 1 for s in slots]
+    for s in slots:
+        kv.ensure(s, kv.seq_lens[s] + 1)
+    toks = torch.randint(0, cfg.vocab, (B,), generator=g,
+                         dtype=torch.int32).to(dev)
+    pos = torch.tensor([l - 1 for l in lens], dtype=torch.int32, device=dev)
+    st = torch.tensor(slots, dtype=torch.int32, device=dev)
+
+    def meta():
+        return AttnMeta(mode="decode", slot_ids=st,
+                        seq_lens=torch.tensor(lens, dtype=torch.int32,
+                                              device=dev),
+                        cu_q=torch.arange(B + 1, dtype=torch.int32,
+                                          device=dev),
+                        logits_idx=torch.arange(B, dtype=torch.long,
+                                                device=dev),
+                        max_q=1, max_kv=max(lens), window=0)
+
+    saved = list(kv.seq_lens)
+    model.fused_chain = False
+    lg = model.forward(toks, pos, kv, st, meta()).float()
+    kv.seq_lens[:] = saved
+    model.fused_chain = True
+    lf = model.forward(toks, pos, kv, st, meta()).float()
+    assert lf.shape == lg.shape == (B, cfg.vocab)
+    atol = rtol = 1e-1
+    for row in range(B):
+        torch.testing.assert_close(lf[row], lg[row], atol=atol, rtol=rtol,
+                                   msg=lambda m, r=row: f"row {r}: {m}")
+    top2 = lg.topk(2, dim=-1).values
+    clear = (top2[:, 0] - top2[:, 1]) > 2 * atol
+    assert torch.equal(lf.argmax(-1)[clear], lg.argmax(-1)[clear])
+
+
 def test_fused_chain_mt2_batch_over_32():
     """Batches 33-64 run the MT2 frag chain (two 32-row halves) and must
     match the generic path token-for-token."""

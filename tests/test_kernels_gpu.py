@@ -12,6 +12,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import fused_oracle as fo
 from ollamamq_amd.ops import reference as ref
 from ollamamq_amd.engine.kvcache import PagedKVCache
 from ollamamq_amd.ops.interface import AttnMeta
@@ -447,18 +448,17 @@ def test_wstream_gemm():
         pk = hip.pack_weight(w)
         assert pk is not None
         y = hip.linear_packed(x, pk, None, N)
-        expect = torch.nn.functional.linear(x, w)
-        torch.testing.assert_close(y.float(), expect.float(),
-                                   atol=8e-2, rtol=8e-2)
+        # fp64 truth, one bf16 ulp + 2^-8 rms (tests/fused_oracle.py): at
+        # K=14336 a single dropped 64-wide k-block moves a result by ~8
+        fo.assert_bf16_close(y, x.double() @ w.double().t(), str((M, N, K)))
     # bias path (qwen qkv)
     M, N, K = 32, 4736, 3584
     x = rnd(M, K, seed=1)
     w = rnd(N, K, seed=2)
     b = rnd(N, seed=3)
     y = hip.linear_packed(x, hip.pack_weight(w), b, N)
-    expect = torch.nn.functional.linear(x, w, b)
-    torch.testing.assert_close(y.float(), expect.float(),
-                               atol=8e-2, rtol=8e-2)
+    fo.assert_bf16_close(y, x.double() @ w.double().t() + b.double(),
+                         "bias")
 
 
 def test_wstream_pack_roundtrip_cpu_check():
@@ -484,11 +484,9 @@ def test_wstream_gu_fused():
         pk = hip.pack_weight_gu(w)
         assert pk is not None
         act = hip.linear_gu(x, pk, 2 * F)
-        gu = torch.nn.functional.linear(x.float(), w.float())
-        g, u = gu[:, :F], gu[:, F:]
-        expect = torch.nn.functional.silu(g) * u
-        torch.testing.assert_close(act.float(), expect,
-                                   atol=8e-2, rtol=8e-2)
+        fo.assert_bf16_close(
+            act, fo.swiglu_oracle(x.double() @ w.double().t()),
+            str((M, F, K)))
 
 
 def _defrag(flat, M, K):
@@ -562,6 +560,6 @@ def test_decode_attn_fragout():
     a_std = hip.attention_decode(q, kv, 0, meta)
     a_fr = hip.attention_decode(q, kv, 0, meta, fragout=True)
     Kh = cfg.n_heads * 128
-    torch.testing.assert_close(_defrag(a_fr, B, Kh),
-                               a_std.view(B, Kh).float().cpu(),
-                               atol=5e-2, rtol=5e-2)
+    # same arithmetic, only the store address differs: bit-equal
+    assert torch.equal(_defrag(a_fr, B, Kh),
+                       a_std.view(B, Kh).float().cpu())
