@@ -604,7 +604,10 @@ extern "C" int argmax_bf16(void* out, const void* logits, int B, int V,
                             void* pb, void* pi, int SP, hipStream_t stream)
 {
     if (SP > 1 && pb != nullptr) {
-        int seg = (V / SP + 2047) & ~2047;          // 256-thread x8 rounds
+        // 256-thread x8 rounds; ceil(V / SP): the floor gave seg = 0 for
+        // V < SP and left the last V % SP tokens unscanned when V / SP
+        // fell just above a multiple of 2048
+        int seg = ((V + SP - 1) / SP + 2047) & ~2047;
         while ((int64_t)(SP - 1) * seg >= V) SP--;  // drop empty slices
         dim3 grid(B, SP);
         k_argmax_part<<<grid, 256, 0, stream>>>(
@@ -773,11 +776,16 @@ extern "C" int row_sumsq_bf16(void* sq, const void* x, int M, int H,
 // (row, v) so partials stay exact).  noise_override (tests): u = that
 // buffer instead of the hash.
 // ---------------------------------------------------------------------------
+// u = (top 23 bits + 0.5) * 2^-23: 2m + 1 < 2^24, so the sum and the
+// scaling are exact in fp32 and u spans [2^-24, 1 - 2^-24].  (24 bits + 0.5
+// is a rounding tie above 2^23 and reaches u == 1, i.e. g = +inf, which
+// wins the argmax whatever its logit.)  The Gumbel noise is therefore
+// finite, within [-2.82, 16.64], for every (seed, ctr, v).
 DEV float u01_hash(uint64_t key) {
     key ^= key >> 33; key *= 0xff51afd7ed558ccdULL;
     key ^= key >> 33; key *= 0xc4ceb9fe1a85ec53ULL;
     key ^= key >> 33;
-    return ((float)(key >> 40) + 0.5f) * (1.0f / 16777216.0f);
+    return ((float)(key >> 41) + 0.5f) * (1.0f / 8388608.0f);
 }
 
 DEV float gumbel_of(uint64_t seed, uint64_t ctr, int v,

@@ -123,6 +123,17 @@ def embedding(tokens, table):
 
 def rmsnorm_residual(x, residual, weight, eps):
     T, H = x.shape
+    # the kernel walks packed rows with 16-byte vectors, at most 8 per
+    # thread: anything else would read the wrong memory, so it is rejected
+    if H % 8 or H > 16384:
+        raise ValueError(f"rmsnorm_residual: H = {H} must be a multiple of "
+                         "8 and at most 16384")
+    if not x.is_contiguous() or not weight.is_contiguous() \
+            or (residual is not None and not residual.is_contiguous()):
+        raise ValueError("rmsnorm_residual: x, residual and weight must be "
+                         "contiguous")
+    if residual is not None and residual.shape != x.shape:
+        raise ValueError("rmsnorm_residual: residual shape differs from x")
     y = torch.empty_like(x)
     res_out = torch.empty_like(x)
     _check(_lib.rmsnorm_residual_bf16(_p(y), _p(res_out), _p(x),
@@ -726,6 +737,9 @@ def linear(x, weight, bias=None, packed=None):
 def swiglu(gate_up):
     T, F2 = gate_up.shape
     F = F2 // 2
+    if F2 % 2 or F % 8:
+        # 16-byte vectors: the kernel would silently drop the F % 8 tail
+        raise ValueError(f"swiglu: F = {F2} / 2 must be a multiple of 8")
     out = torch.empty((T, F), dtype=gate_up.dtype, device=gate_up.device)
     _check(_lib.swiglu_bf16(_p(out), _p(gate_up), T, F, _stream()),
            "swiglu")

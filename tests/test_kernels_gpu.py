@@ -1,11 +1,14 @@
 """Numerics: each gfx950 HIP kernel vs the plain-PyTorch fp32 reference.
 
 Runs only on a real MI355X (pytest -m gpu via gpurun).  Inputs are random
-bf16; the oracle computes in fp32 from the same bf16-rounded values, so
-tolerances cover only the kernel's own bf16 output rounding + fp32
-reduction-order differences.  The attention tests use the fp64 oracle and
-the per-sequence budgets of tests/attn_oracle.py instead (one bf16 ulp +
-2^-8 rms, plus 2^-9 absP for the MFMA prefill's bf16 P).
+bf16; the oracles compute in fp64 from the same bf16-rounded values, so
+the budget (one bf16 ulp + 2^-8 rms, fused_oracle.assert_bf16_close, rms
+per row) covers only the kernel's own bf16 output rounding + fp32
+reduction-order differences; copies and single roundings must be
+bit-equal.  The attention tests use the per-sequence budgets of
+tests/attn_oracle.py (plus 2^-9 absP for the MFMA prefill's bf16 P).
+tests/test_elementwise_gpu.py and tests/test_sampler_kernels_gpu.py hold
+the elementwise and sampler kernels at their edge shapes.
 """
 import math
 
@@ -15,6 +18,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import attn_oracle as ao
+import elem_oracle as eo
 import fused_oracle as fo
 from ollamamq_amd.ops import reference as ref
 from ollamamq_amd.engine.kvcache import PagedKVCache
@@ -42,20 +46,19 @@ def test_rmsnorm_residual():
     for T, H in [(1, 4096), (33, 4096), (256, 512), (7, 8192)]:
         x = rnd(T, H, seed=T)
         res = rnd(T, H, seed=T + 1)
-        w = rnd(H, scale=0.5, seed=T + 2) + 1.0
-        y, r2 = hip.rmsnorm_residual(x, res, w.bfloat16(), 1e-5)
-        y_ref, r_ref = ref.rmsnorm_residual(
-            x.float().cpu(), res.float().cpu(), w.float().cpu(), 1e-5)
-        torch.testing.assert_close(r2.float().cpu(), r_ref.float(),
-                                   atol=2e-2, rtol=2e-2)
-        torch.testing.assert_close(y.float().cpu(), y_ref.float(),
-                                   atol=5e-2, rtol=5e-2)
+        w = (rnd(H, scale=0.5, seed=T + 2) + 1.0).bfloat16()
+        y, r2 = hip.rmsnorm_residual(x, res, w, 1e-5)
+        # res_out is one rounding of the fp32 sum: bit-equal
+        assert torch.equal(r2, (x.float() + res.float()).bfloat16())
+        eo.assert_rows_close(y, eo.rmsnorm_oracle(x.cpu(), res.cpu(),
+                                                  w.cpu(), 1e-5),
+                             f"rmsnorm {T}x{H}")
         # no-residual path
-        y0, r0 = hip.rmsnorm_residual(x, None, w.bfloat16(), 1e-5)
-        y0_ref, _ = ref.rmsnorm_residual(x.float().cpu(), None,
-                                         w.float().cpu(), 1e-5)
-        torch.testing.assert_close(y0.float().cpu(), y0_ref.float(),
-                                   atol=5e-2, rtol=5e-2)
+        y0, r0 = hip.rmsnorm_residual(x, None, w, 1e-5)
+        assert torch.equal(r0, x)
+        eo.assert_rows_close(y0, eo.rmsnorm_oracle(x.cpu(), None, w.cpu(),
+                                                   1e-5),
+                             f"rmsnorm {T}x{H} no residual")
 
 
 def test_rope():
@@ -68,11 +71,11 @@ def test_rope():
     cos, sin = ang.cos().to(dev()), ang.sin().to(dev())
     q = rnd(T, Hq, D, seed=3)
     k = rnd(T, Hk, D, seed=4)
-    q_ref, k_ref = q.float().cpu(), k.float().cpu()
-    ref.rope(q_ref, k_ref, pos.cpu(), cos.cpu(), sin.cpu())
+    q_ref = fo.rope_oracle(q.double().cpu(), pos.cpu(), cos.cpu(), sin.cpu())
+    k_ref = fo.rope_oracle(k.double().cpu(), pos.cpu(), cos.cpu(), sin.cpu())
     hip.rope(q, k, pos, cos, sin)
-    torch.testing.assert_close(q.float().cpu(), q_ref, atol=2e-2, rtol=2e-2)
-    torch.testing.assert_close(k.float().cpu(), k_ref, atol=2e-2, rtol=2e-2)
+    eo.assert_rows_close(q, q_ref, "rope q")
+    eo.assert_rows_close(k, k_ref, "rope k")
 
 
 def make_caches(L=2, KVH=2, D=128, n_pages=64, slots=4, ctx=512):
@@ -278,9 +281,8 @@ def test_swiglu():
     for T, F in [(5, 1024), (64, 14336)]:
         gu = rnd(T, 2 * F, seed=F)
         out = hip.swiglu(gu)
-        out_ref = ref.swiglu(gu.float().cpu())
-        torch.testing.assert_close(out.float().cpu(), out_ref,
-                                   atol=2e-2, rtol=2e-2)
+        eo.assert_rows_close(out, fo.swiglu_oracle(gu.double().cpu()),
+                             f"swiglu {T}x{F}")
 
 
 def test_argmax_sampler():
@@ -353,18 +355,19 @@ def test_fused_rope_append():
     ang = torch.outer(torch.arange(64, dtype=torch.float32),
                       1.0 / 10000 ** (torch.arange(0, D, 2) / D))
     cos, sin = ang.cos().to(dev()), ang.sin().to(dev())
-    q_ref = q.float().cpu().clone()
-    k_ref = k.float().cpu().clone()
-    v_ref = v.float().cpu().clone()
-    ref.rope(q_ref, k_ref, pos.cpu(), cos.cpu(), sin.cpu())
-    ref.kv_append(cc, 0, k_ref, v_ref, slot.cpu(), pos.cpu())
+    q_ref = fo.rope_oracle(q.double().cpu(), pos.cpu(), cos.cpu(), sin.cpu())
+    k_ref = fo.rope_oracle(k.double().cpu(), pos.cpu(), cos.cpu(), sin.cpu())
+    v_src = v.cpu().clone()
     hip.rope_append(gc, 0, q, k, v, pos, slot, cos, sin)
-    torch.testing.assert_close(q.float().cpu(), q_ref, atol=2e-2, rtol=2e-2)
-    torch.testing.assert_close(k.float().cpu(), k_ref, atol=2e-2, rtol=2e-2)
-    torch.testing.assert_close(gc.k_pool.float().cpu(), cc.k_pool,
-                               atol=2e-2, rtol=2e-2)
-    torch.testing.assert_close(gc.v_pool.float().cpu(), cc.v_pool,
-                               atol=0, rtol=0)
+    eo.assert_rows_close(q, q_ref, "rope_append q")
+    eo.assert_rows_close(k, k_ref, "rope_append k")
+    assert torch.equal(v.cpu(), v_src)
+    # the pool holds the rotated k the call returned and the source v, bit
+    # for bit, and nothing else
+    ref.kv_append(cc, 0, k.float().cpu(), v_src.float(), slot.cpu(),
+                  pos.cpu())
+    assert torch.equal(gc.k_pool.float().cpu(), cc.k_pool)
+    assert torch.equal(gc.v_pool.float().cpu(), cc.v_pool)
 
 
 def test_mixed_batch_continuous_batching():

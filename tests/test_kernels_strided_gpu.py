@@ -5,6 +5,8 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import elem_oracle as eo
+import fused_oracle as fo
 from ollamamq_amd.ops import reference as ref
 from ollamamq_amd.engine.kvcache import PagedKVCache
 
@@ -22,13 +24,12 @@ def test_rope_on_fused_qkv_views():
     ang = torch.outer(torch.arange(64, dtype=torch.float32),
                       1.0 / 10000 ** (torch.arange(0, D, 2) / D))
     cos, sin = ang.cos().cuda(), ang.sin().cuda()
-    q_ref = q.float().cpu().clone()
-    k_ref = k.float().cpu().clone()
-    ref.rope(q_ref, k_ref, pos.cpu(), cos.cpu(), sin.cpu())
+    q_ref = fo.rope_oracle(q.double().cpu(), pos.cpu(), cos.cpu(), sin.cpu())
+    k_ref = fo.rope_oracle(k.double().cpu(), pos.cpu(), cos.cpu(), sin.cpu())
     v_before = qkv[:, (Hq + Hk) * D:].clone()
     hip.rope(q, k, pos, cos, sin)
-    torch.testing.assert_close(q.float().cpu(), q_ref, atol=2e-2, rtol=2e-2)
-    torch.testing.assert_close(k.float().cpu(), k_ref, atol=2e-2, rtol=2e-2)
+    eo.assert_rows_close(q, q_ref, "rope q view")
+    eo.assert_rows_close(k, k_ref, "rope k view")
     # v region untouched
     assert torch.equal(qkv[:, (Hq + Hk) * D:], v_before)
 
