@@ -34,8 +34,9 @@ def _newer(target, *sources):
 def build_kernels(force=False):
     import glob
     srcs = sorted(glob.glob(os.path.join(KDIR, "*.hip")))
+    hdrs = glob.glob(os.path.join(KDIR, "*.cuh"))   # included, not compiled
     out = os.path.join(KDIR, "_kernels_gfx950.so")
-    if not force and _newer(out, *srcs):
+    if not force and _newer(out, *srcs, *hdrs):
         print(f"kernels up to date: {out}")
         return out
     _run([

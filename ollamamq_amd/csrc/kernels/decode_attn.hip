@@ -12,44 +12,10 @@
 // LDS: K/V chunk tiles shared by the group's G waves (each KV byte read
 // once per kv-head, not per q-head); rows padded +4 bf16 to keep per-lane
 // row reads conflict-free (guide §6 G4).
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
-#include <cstdint>
-
-typedef __hip_bfloat16 bf16;
-typedef __hip_bfloat162 bf162;
-
-#define DEV static __device__ __forceinline__
-DEV float bf2f(bf16 x) { return __bfloat162float(x); }
-
-DEV void load8f_lds(const bf16* p, float* out) {
-    const bf162* v = reinterpret_cast<const bf162*>(p);
-    float2 f0 = __bfloat1622float2(v[0]), f1 = __bfloat1622float2(v[1]);
-    float2 f2 = __bfloat1622float2(v[2]), f3 = __bfloat1622float2(v[3]);
-    out[0] = f0.x; out[1] = f0.y; out[2] = f1.x; out[3] = f1.y;
-    out[4] = f2.x; out[5] = f2.y; out[6] = f3.x; out[7] = f3.y;
-}
-
-// fused-chain frag layout for the attention OUTPUT (o-GEMM streams it
-// linearly; see wstream_gemm.hip frag_off): element (m, kcol) ->
-// 16 B unit ((b*4+j)*64 + h*32 + m), kcol = b*64 + j*16 + h*8 + e
-DEV int64_t attn_frag_off(int m, int kcol) {
-    const int b = kcol >> 6, j = (kcol >> 4) & 3, h = (kcol >> 3) & 1;
-    return ((((int64_t)b * 4 + j) * 64) + h * 32 + m) * 8 + (kcol & 7);
-}
-
-DEV float wave_max(float x) {
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        x = fmaxf(x, __shfl_down(x, off, 64));
-    return __shfl(x, 0, 64);
-}
-DEV float wave_sum(float x) {
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        x += __shfl_down(x, off, 64);
-    return __shfl(x, 0, 64);
-}
+//
+// fragout: the attention OUTPUT is written in the fused-chain frag layout
+// (common.cuh frag_off) so the o-GEMM streams it linearly.
+#include "common.cuh"
 
 #define DCHUNK 64
 #define DHEAD 128
@@ -140,8 +106,7 @@ __global__ __launch_bounds__(GT * 64, 1) void k_decode_attn(
     auto src_of = [&](int base, int u) -> int64_t {
         const int tok = u / (DHEAD / 8), dv = u % (DHEAD / 8);
         const int tk = base + tok < kv_len ? base + tok : kv_len - 1;
-        const int gp = page_table[(int64_t)slot * max_pages + tk / page];
-        return (((int64_t)gp * KVH + kvh) * page + tk % page) * DHEAD
+        return paged_kv_row(page_table, slot, max_pages, tk, page, KVH, kvh)
                + dv * 8;
     };
     auto stage_direct = [&](int ch2) {
@@ -218,7 +183,7 @@ __global__ __launch_bounds__(GT * 64, 1) void k_decode_attn(
             #pragma unroll
             for (int d = 0; d < DHEAD; d += 8) {
                 float k8[8];
-                load8f_lds(krow + d, k8);
+                load8f(krow + d, k8);
                 s += k8[0] * qrow[d] + k8[1] * qrow[d + 1]
                    + k8[2] * qrow[d + 2] + k8[3] * qrow[d + 3]
                    + k8[4] * qrow[d + 4] + k8[5] * qrow[d + 5]
@@ -228,13 +193,13 @@ __global__ __launch_bounds__(GT * 64, 1) void k_decode_attn(
         }
 
         // ---- online softmax ----
-        const float smax = wave_max(s);
+        const float smax = wave_reduce_max(s);
         float p = 0.f;
         if (smax > -3.0e38f) {
             const float mn = fmaxf(m, smax);
             const float corr = __expf(m - mn);
             p = live ? __expf(s - mn) : 0.f;
-            l = l * corr + wave_sum(p);
+            l = l * corr + wave_reduce_sum(p);
             o0 *= corr; o1 *= corr;
             m = mn;
         }
@@ -288,7 +253,7 @@ __global__ __launch_bounds__(GT * 64, 1) void k_decode_attn(
         if (fragout)
             *reinterpret_cast<bf162*>(
                 out + (int64_t)(S_idx >> 5) * 32 * Hq * DHEAD
-                    + attn_frag_off(S_idx & 31, qh * DHEAD + 2 * lane))
+                    + frag_off(S_idx & 31, qh * DHEAD + 2 * lane))
                 = ov;
         else
             reinterpret_cast<bf162*>(
@@ -351,7 +316,7 @@ __global__ __launch_bounds__(GT * 64, 1) void k_decode_attn(
         if (fragout) {
             *reinterpret_cast<bf162*>(
                 out + (int64_t)(S_idx >> 5) * 32 * Hq * DHEAD
-                    + attn_frag_off(S_idx & 31, qh * DHEAD + 2 * lane)) =
+                    + frag_off(S_idx & 31, qh * DHEAD + 2 * lane)) =
                 __float22bfloat162_rn(
                     make_float2(a0 * linv, a1 * linv));
             return;
@@ -391,8 +356,8 @@ __global__ __launch_bounds__(256) void k_decode_combine(
     if (fragout)
         *reinterpret_cast<bf162*>(
             out + (int64_t)((sh / Hq) >> 5) * 32 * Hq * DHEAD
-                + attn_frag_off((sh / Hq) & 31,
-                                (sh % Hq) * DHEAD + 2 * lane)) = ov;
+                + frag_off((sh / Hq) & 31,
+                           (sh % Hq) * DHEAD + 2 * lane)) = ov;
     else
         reinterpret_cast<bf162*>(out + (int64_t)sh * DHEAD)[lane] = ov;
 }
@@ -471,11 +436,8 @@ __global__ __launch_bounds__(256) void k_decode_pure(
         for (int u = threadIdx.x; u < nslot; u += 256) {
             const int tok = u >> 4, dv = u & 15;
             const int tk = base + tok < kv_len ? base + tok : kv_len - 1;
-            const int gp = page_table[(int64_t)slot * max_pages
-                                      + tk / page];
-            const int64_t src =
-                (((int64_t)gp * KVH + kvh) * page + tk % page) * 128
-                + dv * 8;
+            const int64_t src = paged_kv_row(page_table, slot, max_pages, tk,
+                                             page, KVH, kvh) + dv * 8;
             const uint4 k = *reinterpret_cast<const uint4*>(kpool + src);
             const uint4 v = *reinterpret_cast<const uint4*>(vpool + src);
             acc ^= k.x ^ k.w ^ v.x ^ v.w;

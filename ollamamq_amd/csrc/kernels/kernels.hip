@@ -15,29 +15,7 @@
 // Exposed as extern "C" launchers taking raw device pointers + hipStream_t,
 // bound from Python via ctypes (ops/hip.py) — no torch ABI dependency.
 
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
-#include <cstdint>
-
-typedef __hip_bfloat16 bf16;
-typedef __hip_bfloat162 bf162;
-
-#define DEV static __device__ __forceinline__
-
-DEV float bf2f(bf16 x) { return __bfloat162float(x); }
-DEV bf16 f2bf(float x) { return __float2bfloat16(x); }
-
-struct short8 { short4 lo, hi; };
-
-// load 8 bf16 (16 B) and widen to 8 floats
-DEV void load8f(const bf16* p, float* out) {
-    const bf162* v = reinterpret_cast<const bf162*>(p);
-    bf162 a = v[0], b = v[1], c = v[2], d = v[3];
-    float2 fa = __bfloat1622float2(a), fb = __bfloat1622float2(b);
-    float2 fc = __bfloat1622float2(c), fd = __bfloat1622float2(d);
-    out[0] = fa.x; out[1] = fa.y; out[2] = fb.x; out[3] = fb.y;
-    out[4] = fc.x; out[5] = fc.y; out[6] = fd.x; out[7] = fd.y;
-}
+#include "common.cuh"
 
 DEV void store8bf(bf16* p, const float* in) {
     bf162* v = reinterpret_cast<bf162*>(p);
@@ -45,20 +23,6 @@ DEV void store8bf(bf16* p, const float* in) {
     v[1] = __float22bfloat162_rn(make_float2(in[2], in[3]));
     v[2] = __float22bfloat162_rn(make_float2(in[4], in[5]));
     v[3] = __float22bfloat162_rn(make_float2(in[6], in[7]));
-}
-
-DEV float wave_reduce_sum(float x) {
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        x += __shfl_down(x, off, 64);
-    return __shfl(x, 0, 64);
-}
-
-DEV float wave_reduce_max(float x) {
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-        x = fmaxf(x, __shfl_down(x, off, 64));
-    return __shfl(x, 0, 64);
 }
 
 // ---------------------------------------------------------------------------
@@ -187,8 +151,8 @@ extern "C" int rope_bf16(
 
 // ---------------------------------------------------------------------------
 // Paged-KV append: scatter k/v [T,KVH,D] to pool[layer] at (slot,pos).
-// Pool layout [P][KVH][page][D] bf16; one wave per (token, head);
-// lane moves 2 elems (D=128).
+// Pool layout and addressing: common.cuh paged_kv_row.  One wave per
+// (token, head); lane moves 2 elems (D=128).
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_kv_append(
     bf16* __restrict__ kp, bf16* __restrict__ vp,
@@ -201,10 +165,8 @@ __global__ __launch_bounds__(256) void k_kv_append(
     const int lane = threadIdx.x & 63;
     if (gid >= T * KVH) return;
     const int t = gid / KVH, h = gid % KVH;
-    const int p = pos[t];
-    const int pg = page_table[(int64_t)slot[t] * max_pages + p / page];
-    const int off = p % page;
-    const int64_t dst = (((int64_t)pg * KVH + h) * page + off) * D;
+    const int64_t dst = paged_kv_row(page_table, slot[t], max_pages, pos[t],
+                                     page, KVH, h);
     const int64_t src = (int64_t)t * src_stride + (int64_t)h * D;
     const bf162* ks = reinterpret_cast<const bf162*>(k + src);
     const bf162* vs = reinterpret_cast<const bf162*>(v + src);
@@ -318,10 +280,9 @@ __global__ __launch_bounds__(512) void k_paged_attn(
                 const int tok = u / (DHEAD / 8);
                 const int dv = u % (DHEAD / 8);
                 if (base + tok < kv_len) {
-                    const int gp = page_table[(int64_t)slot * max_pages
-                                              + (base + tok) / page];
-                    const int64_t src = (((int64_t)gp * KVH + kvh) * page
-                                         + (base + tok) % page) * DHEAD + dv * 8;
+                    const int64_t src =
+                        paged_kv_row(page_table, slot, max_pages, base + tok,
+                                     page, KVH, kvh) + dv * 8;
                     *reinterpret_cast<uint4*>(k_tile + tok * KROW + dv * 8) =
                         *reinterpret_cast<const uint4*>(kpool + src);
                     *reinterpret_cast<uint4*>(v_tile + tok * KROW + dv * 8) =
@@ -652,12 +613,14 @@ __global__ __launch_bounds__(256) void k_rope_append(
         base[lane + d2] = f2bf(x2 * c + x1 * s);
         return;
     }
-    const int pg = page_table[(int64_t)slot[t] * max_pages + p / page];
-    const int off = p % page;
-    if (h < Hq + KVH) {                  // k head: rope + pool write
+    const bool is_k = h < Hq + KVH;
+    // pool row of this token for kv-head (h - Hq) or (h - Hq - KVH)
+    const int64_t row = paged_kv_row(page_table, slot[t], max_pages, p, page,
+                                     KVH, is_k ? h - Hq : h - Hq - KVH);
+    if (is_k) {                          // k head: rope + pool write
         const int kh = h - Hq;
         bf16* base = k + (int64_t)t * ks + (int64_t)kh * D;
-        bf16* dst = kp + (((int64_t)pg * KVH + kh) * page + off) * D;
+        bf16* dst = kp + row;
         const float c = cost[(int64_t)p * d2 + lane];
         const float s = sint[(int64_t)p * d2 + lane];
         const float x1 = bf2f(base[lane]);
@@ -674,8 +637,7 @@ __global__ __launch_bounds__(256) void k_rope_append(
         const int vh = h - Hq - KVH;
         const bf162* src = reinterpret_cast<const bf162*>(
             v + (int64_t)t * vs + (int64_t)vh * D);
-        bf162* dst = reinterpret_cast<bf162*>(
-            vp + (((int64_t)pg * KVH + vh) * page + off) * D);
+        bf162* dst = reinterpret_cast<bf162*>(vp + row);
         dst[lane] = src[lane];
     }
 }
@@ -902,7 +864,7 @@ extern "C" int sample_gumbel_bf16(
 // ---------------------------------------------------------------------------
 // Fragify + row sum-of-squares: convert a standard [M, H] activation into
 // the 32-row MFMA fragment layout the fused decode chain streams
-// (wstream_gemm.hip frag_off) AND emit sq[m] = sum(x[m]^2) — one read of
+// (common.cuh frag_off) AND emit sq[m] = sum(x[m]^2) — one read of
 // the embedding output seeds the whole chain.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_fragify_sumsq(
@@ -915,17 +877,13 @@ __global__ __launch_bounds__(256) void k_fragify_sumsq(
     bf16* xfh = xf + (int64_t)(m >> 5) * 32 * H;
     const int mr = m & 31;
     float s = 0.f;
-    // 16-byte chunk c covers k = c*8..c*8+8: frag unit
-    // ((c>>3)*4 + ((c>>1)&3))*64 + (c&1)*32 + mr
-    for (int c = threadIdx.x; c < H / 8; c += 256) {
+    for (int c = threadIdx.x; c < H / 8; c += 256) {   // 16-byte chunks
         const uint4 v = *reinterpret_cast<const uint4*>(row + c * 8);
         float f[8];
         load8f(row + c * 8, f);
         #pragma unroll
         for (int e = 0; e < 8; e++) s += f[e] * f[e];
-        const int64_t u = ((int64_t)(c >> 3) * 4 + ((c >> 1) & 3)) * 64
-                          + (c & 1) * 32 + mr;
-        *reinterpret_cast<uint4*>(xfh + u * 8) = v;
+        *reinterpret_cast<uint4*>(xfh + frag_unit(mr, c) * 8) = v;
     }
     __shared__ float red[4];
     s = wave_reduce_sum(s);

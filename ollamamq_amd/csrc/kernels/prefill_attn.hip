@@ -15,21 +15,12 @@
 //       is stored TRANSPOSED at staging time so both PV fragments are
 //       contiguous 16-byte ds reads.
 //
-// A/B/C fragment maps (verified numerically by the skinny-GEMM tests):
+// A/B/C fragment maps (verified numerically by the fused-epilogue tier-A
+// tests and the attention key probes):
 //   A: row = lane&31,  k = (lane>>5)*8 + j
 //   B: col = lane&31,  k = (lane>>5)*8 + j
 //   C: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
-#include <cstdint>
-
-typedef __hip_bfloat16 bf16;
-typedef __hip_bfloat162 bf162;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-#define DEV static __device__ __forceinline__
-[[maybe_unused]] DEV float bf2f(bf16 x) { return __bfloat162float(x); }
+#include "common.cuh"
 
 #define PF_CHUNK 64          // kv tokens per staged chunk
 #define PF_ROWS 32           // q rows per tile
@@ -121,10 +112,8 @@ __global__ __launch_bounds__(512) void k_prefill_attn(
             const int tok = u / (DH / 8);
             const int dv = u % (DH / 8);
             const int tk = base + tok < kv_len ? base + tok : kv_len - 1;
-            const int gp = page_table[(int64_t)slot * max_pages
-                                      + tk / page];
-            const int64_t src = (((int64_t)gp * KVH + kvh) * page
-                                 + tk % page) * DH + dv * 8;
+            const int64_t src = paged_kv_row(page_table, slot, max_pages, tk,
+                                             page, KVH, kvh) + dv * 8;
             stK[pi] = *reinterpret_cast<const uint4*>(kpool + src);
             stV[pi] = *reinterpret_cast<const uint4*>(vpool + src);
         }

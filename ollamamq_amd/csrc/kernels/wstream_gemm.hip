@@ -5,16 +5,17 @@
 // round-1 measured hipBLASLt at 1.8-4.6 TB/s on these shapes with a
 // ~19 us floor on qkv/o (profiles/r01_decode_step_budget.md).  Two
 // hand-written attempts also lost:
-//  * fragment-direct (skinny_gemm.hip): MFMA-layout loads are 16 B/lane at
-//    8 KB row stride -> cold misses over-fetched ~4x;
+//  * fragment-direct (removed; measured history in NOTES.md): MFMA-layout
+//    loads are 16 B/lane at 8 KB row stride -> cold misses over-fetched
+//    ~4x;
 //  * LDS-staged: full-line loads, but __syncthreads() carries a vmcnt(0)
 //    (cdna_hip_programming.md "Pipelining across barriers"), draining the
 //    prefetch ring every chunk -> 87% SQ_WAIT_ANY.
 //
 // This kernel removes the conflict at the source: the weights are OURS,
 // so they are stored pre-packed in MFMA fragment order (ops/hip.py
-// pack_weight).  Element W[n][k] with n = t*32+r, k = b*64 + j*16 + h*8 + e
-// lives at packed uint4 index ((t*NB + b)*4 + j)*64 + (h*32 + r), e inside.
+// pack_weight): each 32-row tile t of W is one frag-layout image
+// (common.cuh), tiles back to back.
 // The stream is then PERFECTLY linear: each wave reads consecutive 1 KiB
 // vectors (full 128 B line use per instruction), tagged non-temporal
 // (MI355X_MICROARCH "nt-weights": one-time-read stream, -18% landed
@@ -27,30 +28,15 @@
 // any K%64==0, N%32==0, M<=64).  Wave partials meet in a single
 // end-of-kernel LDS reduce (the ONE barrier, after all streaming).
 // ksplit>1 writes fp32 partials; k_wstream_combine folds them (+bias).
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
-#include <cstdint>
+//
+// Activations may arrive and leave in the frag layout (XLDS=2 / yfrag):
+// the same fragment order applied to a [32, K] activation, defined with
+// frag_off in common.cuh.
+#include "common.cuh"
 
-typedef __hip_bfloat16 bf16;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 
 union u4bf8 { u32x4 u; bf16x8 v; };
-
-// Activation-fragment layout ("frag"): the SAME MFMA fragment order the
-// weight packs use, applied to a [32, K] activation: element (m, k) with
-// k = b*64 + j*16 + h*8 + e lives at 16-byte unit ((b*4 + j)*64 + h*32
-// + m), elem e.  Producers (GEMM epilogues, decode-attention combine,
-// the embedding fragify kernel) write it; consumers stream it LINEARLY
-// exactly like packed weights — the per-iteration x machinery (32-line
-// scattered loads or LDS staging, measured 15-30% on top of the pure
-// stream) disappears.  Buffers are always 32 rows; rows >= M hold
-// garbage that MFMA carries in dead accumulator rows (never stored).
-static __device__ __forceinline__ int64_t frag_off(int m, int kcol) {
-    const int b = kcol >> 6, j = (kcol >> 4) & 3, h = (kcol >> 3) & 1;
-    return ((((int64_t)b * 4 + j) * 64) + h * 32 + m) * 8 + (kcol & 7);
-}
 
 // Pure-stream diagnostic: same grid/geometry/addressing as the GEMM but
 // only the nt weight loads (no x, no MFMA) — measures this geometry's
@@ -134,6 +120,22 @@ struct RopeEpi {
     bf16* vp;
     int nl, nkl, psz, maxp;
 };
+
+// Spill one wave's 32x32 fp32 accumulator tile (MFMA C layout: col =
+// lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)) to its red8 slab for the
+// cross-wave reduce.  The leading barrier closes whatever read smem last
+// (the streaming epoch's x tiles, or the previous m-tile's reduce); the
+// trailing one publishes all 8 slabs.
+DEV void spill_acc(float (*red8)[32][32], const f32x16& acc, int wid,
+                   int lane) {
+    __syncthreads();
+    #pragma unroll
+    for (int r = 0; r < 16; r++) {
+        const int crow = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        red8[wid][crow][lane & 31] = acc[r];
+    }
+    __syncthreads();
+}
 
 template <int MT, int DEPTH = 1, int XLDS = 0, int GU = 0, int RP = 0>
 __global__ __launch_bounds__(512) void k_wstream_gemm(
@@ -345,14 +347,7 @@ __global__ __launch_bounds__(512) void k_wstream_gemm(
     if (GU) {
         const int F = N >> 1;                  // ffn width
         for (int mt = 0; mt < MT; ++mt) {
-            const f32x16& acc = mt ? acc1 : acc0;
-            __syncthreads();
-            #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int crow = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                red8[wid][crow][lane & 31] = acc[r];
-            }
-            __syncthreads();
+            spill_acc(red8, mt ? acc1 : acc0, wid, lane);
             const int m = tid >> 4, c = tid & 15;  // 512 thr = 32 x 16
             const int gm = m + mt * 32;
             if (gm < M) {
@@ -378,14 +373,7 @@ __global__ __launch_bounds__(512) void k_wstream_gemm(
     if (RP) {
         const int qt = rp.nl * 4, kt = rp.nkl * 4;   // tiles per section
         for (int mt = 0; mt < MT; ++mt) {
-            const f32x16& acc = mt ? acc1 : acc0;
-            __syncthreads();
-            #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int crow = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                red8[wid][crow][lane & 31] = acc[r];
-            }
-            __syncthreads();
+            spill_acc(red8, mt ? acc1 : acc0, wid, lane);
             if (t < qt + kt) {
                 // pair-packed q/k tile: cols {d0+c, d0+64+c}, c<16
                 const int m = tid >> 4, c = tid & 15;
@@ -419,11 +407,9 @@ __global__ __launch_bounds__(512) void k_wstream_gemm(
                         qr[d0 + c] = __float2bfloat16(rlo);
                         qr[64 + d0 + c] = __float2bfloat16(rhi);
                     } else {               // k: rotated, straight to pool
-                        const int pg = rp.ptab[rp.slot[gm] * rp.maxp
-                                               + p / rp.psz];
-                        bf16* dst = rp.kp
-                            + (((int64_t)pg * rp.nkl + head) * rp.psz
-                               + p % rp.psz) * 128;
+                        bf16* dst = rp.kp + paged_kv_row(
+                            rp.ptab, rp.slot[gm], rp.maxp, p, rp.psz,
+                            rp.nkl, head);
                         dst[d0 + c] = __float2bfloat16(rlo);
                         dst[64 + d0 + c] = __float2bfloat16(rhi);
                     }
@@ -446,12 +432,9 @@ __global__ __launch_bounds__(512) void k_wstream_gemm(
                         if (rstd_parts) sv *= rstd_sh[gm];
                         if (bias)
                             sv += __bfloat162float(bias[t * 32 + n]);
-                        const int p = rp.pos[gm];
-                        const int pg = rp.ptab[rp.slot[gm] * rp.maxp
-                                               + p / rp.psz];
-                        bf16* dst = rp.vp
-                            + (((int64_t)pg * rp.nkl + head) * rp.psz
-                               + p % rp.psz) * 128;
+                        bf16* dst = rp.vp + paged_kv_row(
+                            rp.ptab, rp.slot[gm], rp.maxp, rp.pos[gm],
+                            rp.psz, rp.nkl, head);
                         dst[d0 + n] = __float2bfloat16(sv);
                     }
                 }
@@ -459,17 +442,9 @@ __global__ __launch_bounds__(512) void k_wstream_gemm(
         }
         return;
     }
-    __syncthreads();
     const int n0 = t * 32;
     for (int mt = 0; mt < MT; ++mt) {
-        const f32x16& acc = mt ? acc1 : acc0;
-        if (mt) __syncthreads();
-        #pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const int crow = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            red8[wid][crow][lane & 31] = acc[r];
-        }
-        __syncthreads();
+        spill_acc(red8, mt ? acc1 : acc0, wid, lane);
         float rsq[2] = {0.f, 0.f};
         #pragma unroll
         for (int ee = 0; ee < 2; ee++) {
@@ -518,6 +493,41 @@ __global__ __launch_bounds__(512) void k_wstream_gemm(
     }
 }
 
+// Host-side bundle of k_wstream_gemm's runtime arguments: the extern "C"
+// entry points fill it once and only choose template arguments.
+struct WsArgs {
+    void* y;
+    void* part;
+    const void* x;
+    const void* wp;
+    const void* bias;
+    int M, N, K;
+    int64_t xs;
+    int ksplit;
+    const void* rstd_parts;
+    int rstd_nt;
+    float inv_h, eps;
+    const void* res_in;
+    void* sq_parts;
+    RopeEpi rp;
+    int yfrag;
+};
+
+// The one launch site.  Dynamic LDS: the 8-wave reduce space (32 KiB), or
+// the 8 double-buffered 4 KiB x tiles it aliases when XLDS == 1 (64 KiB),
+// plus the 256 B rstd tail.
+template <int MT, int DEPTH, int XLDS, int GU, int RP>
+static void ws_launch(const WsArgs& a, hipStream_t stream)
+{
+    const int lds = (XLDS == 1 ? 16 * 4096 : 8 * 32 * 32 * 4) + 256;
+    dim3 grid(a.N / 32, a.ksplit);
+    k_wstream_gemm<MT, DEPTH, XLDS, GU, RP><<<grid, 512, lds, stream>>>(
+        (bf16*)a.y, (float*)a.part, (const bf16*)a.x, (const u32x4*)a.wp,
+        (const bf16*)a.bias, a.M, a.N, a.K, a.xs, a.ksplit,
+        (const float*)a.rstd_parts, a.rstd_nt, a.inv_h, a.eps,
+        (const bf16*)a.res_in, (float*)a.sq_parts, a.rp, a.yfrag);
+}
+
 // Fused gate_up @ SwiGLU over GU-interleaved packed weights.
 // N = 2F total weight rows; output is the activation [M, F].
 // rstd_parts: optional fused-rmsnorm scale of the raw-residual input.
@@ -526,40 +536,24 @@ extern "C" int wstream_gu_bf16(
     int64_t xs, int xlds, const void* rstd_parts, int rstd_nt,
     float inv_h, float eps, int yfrag, hipStream_t stream)
 {
-    dim3 grid(N / 32, 1);
-    const int lds = (xlds == 1 ? 16 * 4096 : 8 * 32 * 32 * 4) + 256;
+    const WsArgs a{act, nullptr, x, wp, nullptr, M, N, K, xs, 1,
+                   rstd_parts, rstd_nt, inv_h, eps, nullptr, nullptr, {},
+                   yfrag};
     if (M > 32) {
-        if (xlds == 2) {       // frag chain at batches 33..64
-            k_wstream_gemm<2, 1, 2, 1><<<grid, 512, lds, stream>>>(
-                (bf16*)act, nullptr, (const bf16*)x, (const u32x4*)wp,
-                nullptr, M, N, K, xs, 1, (const float*)rstd_parts,
-                rstd_nt, inv_h, eps, nullptr, nullptr, {}, yfrag);
-            return (int)hipGetLastError();
-        }
-        // generic-path fused gate_up+SwiGLU, direct x loads (unused by
-        // default: measured below lib at 64 users)
-        if (rstd_parts || yfrag) return -102;
-        k_wstream_gemm<2, 1, 0, 1><<<grid, 512, lds, stream>>>(
-            (bf16*)act, nullptr, (const bf16*)x, (const u32x4*)wp,
-            nullptr, M, N, K, xs, 1, nullptr, 0, 0.f, 0.f,
-            nullptr, nullptr, {}, 0);
-        return (int)hipGetLastError();
-    }
-    if (xlds == 2)
-        k_wstream_gemm<1, 1, 2, 1><<<grid, 512, lds, stream>>>(
-            (bf16*)act, nullptr, (const bf16*)x, (const u32x4*)wp,
-            nullptr, M, N, K, xs, 1, (const float*)rstd_parts, rstd_nt,
-            inv_h, eps, nullptr, nullptr, {}, yfrag);
+        if (xlds == 2)         // frag chain at batches 33..64
+            ws_launch<2, 1, 2, 1, 0>(a, stream);
+        else if (rstd_parts || yfrag)
+            return -102;       // fusion needs the frag path at MT2
+        else
+            // generic-path fused gate_up+SwiGLU, direct x loads (unused
+            // by default: measured below lib at 64 users)
+            ws_launch<2, 1, 0, 1, 0>(a, stream);
+    } else if (xlds == 2)
+        ws_launch<1, 1, 2, 1, 0>(a, stream);
     else if (xlds == 1)
-        k_wstream_gemm<1, 1, 1, 1><<<grid, 512, lds, stream>>>(
-            (bf16*)act, nullptr, (const bf16*)x, (const u32x4*)wp,
-            nullptr, M, N, K, xs, 1, (const float*)rstd_parts, rstd_nt,
-            inv_h, eps, nullptr, nullptr, {}, yfrag);
+        ws_launch<1, 1, 1, 1, 0>(a, stream);
     else
-        k_wstream_gemm<1, 1, 0, 1><<<grid, 512, lds, stream>>>(
-            (bf16*)act, nullptr, (const bf16*)x, (const u32x4*)wp,
-            nullptr, M, N, K, xs, 1, (const float*)rstd_parts, rstd_nt,
-            inv_h, eps, nullptr, nullptr, {}, yfrag);
+        ws_launch<1, 1, 0, 1, 0>(a, stream);
     return (int)hipGetLastError();
 }
 
@@ -631,52 +625,31 @@ extern "C" int wstream_gemm_bf16(
     const void* rstd_parts, int rstd_nt, float inv_h, float eps,
     const void* res_in, void* sq_parts, int yfrag, hipStream_t stream)
 {
-    dim3 grid(N / 32, ksplit);
-    const int lds_red = 8 * 32 * 32 * 4 + 256;     // reduce + rstd tail
-    const int lds_x = 16 * 4096 + 256;             // + 8x2 x tiles
-    const float* rp = (const float*)rstd_parts;
-    const bf16* ri = ksplit == 1 ? (const bf16*)res_in : nullptr;
-    float* sq = ksplit == 1 ? (float*)sq_parts : nullptr;
     if (ksplit > 1 && rstd_parts) return -100;     // fused rstd needs ks==1
+    // the residual add and the sq partials belong to whoever writes y:
+    // this kernel at ksplit == 1, the tile combine below otherwise
+    const WsArgs a{y, part, x, wp, bias, M, N, K, xs, ksplit,
+                   rstd_parts, rstd_nt, inv_h, eps,
+                   ksplit == 1 ? res_in : nullptr,
+                   ksplit == 1 ? sq_parts : nullptr, {}, yfrag};
     if (M <= 32) {
         if (xlds == 2)
-            k_wstream_gemm<1, 1, 2><<<grid, 512, lds_red, stream>>>(
-                (bf16*)y, (float*)part, (const bf16*)x, (const u32x4*)wp,
-                (const bf16*)bias, M, N, K, xs, ksplit, rp, rstd_nt,
-                inv_h, eps, ri, sq, {}, yfrag);
+            ws_launch<1, 1, 2, 0, 0>(a, stream);
         else if (xlds == 1)
-            k_wstream_gemm<1, 1, 1><<<grid, 512, lds_x, stream>>>(
-                (bf16*)y, (float*)part, (const bf16*)x, (const u32x4*)wp,
-                (const bf16*)bias, M, N, K, xs, ksplit, rp, rstd_nt,
-                inv_h, eps, ri, sq, {}, yfrag);
+            ws_launch<1, 1, 1, 0, 0>(a, stream);
         else if (depth == 2)
-            k_wstream_gemm<1, 2><<<grid, 512, lds_red, stream>>>(
-                (bf16*)y, (float*)part, (const bf16*)x, (const u32x4*)wp,
-                (const bf16*)bias, M, N, K, xs, ksplit, rp, rstd_nt,
-                inv_h, eps, ri, sq, {}, yfrag);
+            ws_launch<1, 2, 0, 0, 0>(a, stream);
         else
-            k_wstream_gemm<1, 1><<<grid, 512, lds_red, stream>>>(
-                (bf16*)y, (float*)part, (const bf16*)x, (const u32x4*)wp,
-                (const bf16*)bias, M, N, K, xs, ksplit, rp, rstd_nt,
-                inv_h, eps, ri, sq, {}, yfrag);
+            ws_launch<1, 1, 0, 0, 0>(a, stream);
     } else {
-        if (xlds == 2) {
-            k_wstream_gemm<2, 1, 2><<<grid, 512, lds_red, stream>>>(
-                (bf16*)y, (float*)part, (const bf16*)x, (const u32x4*)wp,
-                (const bf16*)bias, M, N, K, xs, ksplit, rp, rstd_nt,
-                inv_h, eps, ri, sq, {}, yfrag);
-        } else if (rstd_parts || res_in || sq_parts || yfrag) {
+        if (xlds == 2)
+            ws_launch<2, 1, 2, 0, 0>(a, stream);
+        else if (rstd_parts || res_in || sq_parts || yfrag)
             return -101;           // fusion needs the frag path at MT2
-        } else if (depth == 2)
-            k_wstream_gemm<2, 2><<<grid, 512, lds_red, stream>>>(
-                (bf16*)y, (float*)part, (const bf16*)x, (const u32x4*)wp,
-                (const bf16*)bias, M, N, K, xs, ksplit, nullptr, 0,
-                0.f, 0.f, nullptr, nullptr);
+        else if (depth == 2)
+            ws_launch<2, 2, 0, 0, 0>(a, stream);
         else
-            k_wstream_gemm<2, 1><<<grid, 512, lds_red, stream>>>(
-                (bf16*)y, (float*)part, (const bf16*)x, (const u32x4*)wp,
-                (const bf16*)bias, M, N, K, xs, ksplit, nullptr, 0,
-                0.f, 0.f, nullptr, nullptr);
+            ws_launch<2, 1, 0, 0, 0>(a, stream);
     }
     if (ksplit > 1) {
         if (res_in || sq_parts) {
@@ -707,26 +680,17 @@ extern "C" int wstream_qkv_rope_bf16(
     const void* slot, const void* ptab, void* kp, void* vp,
     int nl, int nkl, int psz, int maxp, int xf, hipStream_t stream)
 {
-    dim3 grid(N / 32, 1);
-    const int lds = 8 * 32 * 32 * 4 + 256;
-    RopeEpi rp{(const float*)rcos, (const float*)rsin, (const int*)pos,
-               (const int*)slot, (const int*)ptab, (bf16*)kp, (bf16*)vp,
-               nl, nkl, psz, maxp};
+    const RopeEpi rp{(const float*)rcos, (const float*)rsin,
+                     (const int*)pos, (const int*)slot, (const int*)ptab,
+                     (bf16*)kp, (bf16*)vp, nl, nkl, psz, maxp};
+    const WsArgs a{y, nullptr, x, wp, bias, M, N, K, xs, 1,
+                   rstd_parts, rstd_nt, inv_h, eps, nullptr, nullptr, rp,
+                   0};
     if (xf && M > 32)
-        k_wstream_gemm<2, 1, 2, 0, 1><<<grid, 512, lds, stream>>>(
-            (bf16*)y, nullptr, (const bf16*)x, (const u32x4*)wp,
-            (const bf16*)bias, M, N, K, xs, 1, (const float*)rstd_parts,
-            rstd_nt, inv_h, eps, nullptr, nullptr, rp);
+        ws_launch<2, 1, 2, 0, 1>(a, stream);
     else if (xf)
-        k_wstream_gemm<1, 1, 2, 0, 1><<<grid, 512, lds, stream>>>(
-            (bf16*)y, nullptr, (const bf16*)x, (const u32x4*)wp,
-            (const bf16*)bias, M, N, K, xs, 1, (const float*)rstd_parts,
-            rstd_nt, inv_h, eps, nullptr, nullptr, rp);
+        ws_launch<1, 1, 2, 0, 1>(a, stream);
     else
-        k_wstream_gemm<1, 1, 0, 0, 1><<<grid, 512, lds, stream>>>(
-            (bf16*)y, nullptr, (const bf16*)x, (const u32x4*)wp,
-            (const bf16*)bias, M, N, K, xs, 1, (const float*)rstd_parts,
-            rstd_nt, inv_h, eps, nullptr, nullptr, rp);
+        ws_launch<1, 1, 0, 0, 1>(a, stream);
     return (int)hipGetLastError();
 }
-

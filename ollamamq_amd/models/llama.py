@@ -414,8 +414,10 @@ class LlamaModel:
         h, _ = ops.rmsnorm_residual(h, None, self.final_norm, cfg.norm_eps)
         if return_hidden:
             return h
-        # NB: no packed= — the MT2 streaming GEMM loses to the library
-        # above batch 32 (doubled x scatter); the fused chain covers <=32
+        # NB: no packed= — this generic path only sees decode batches
+        # above 64 rows, prefill, or a model without the fused chain (which
+        # covers decode up to 64 rows), and the direct-load MT2 streaming
+        # GEMM loses to the library above batch 32 (doubled x scatter)
         logits = ops.linear(h, self.lm_head)
         if self.tp_size > 1:
             # vocab-parallel logits: all-gather shards on the last dim
@@ -426,8 +428,10 @@ class LlamaModel:
 
     def _forward_decode_fused(self, tokens, positions, kv_cache, slot_ids,
                               attn_meta):
-        """Decode step as a fused weight-streaming chain (tp=1, B<=32):
-        4 GEMM-class kernels per layer, zero rmsnorm/swiglu kernels.
+        """Decode step as a fused weight-streaming chain (tp=1, B<=64;
+        rows 33..64 take the MT=2 frag kernels over a second 32-row frag
+        buffer): 4 GEMM-class kernels per layer, zero rmsnorm/swiglu
+        kernels.
         rmsnorm weights are folded into the packs; the rstd scale rides
         each consumer GEMM's epilogue from sum-of-squares partials the
         producer GEMM emitted; residual adds happen in place inside the

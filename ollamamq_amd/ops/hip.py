@@ -25,6 +25,42 @@ _lib = None
 _load_err: Optional[str] = None
 
 
+def _signatures():
+    """extern "C" entry point -> argtypes (the trailing vp is the stream)."""
+    vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+    i64 = ctypes.c_int64
+    return {
+        "rmsnorm_residual_bf16": [vp, vp, vp, vp, vp, i, i, f, vp],
+        "rope_bf16": [vp, vp, vp, vp, vp, i, i, i, i, i64, i64, vp],
+        "kv_append_bf16": [vp, vp, vp, vp, vp, vp, vp,
+                           i, i, i, i, i, i64, vp],
+        "paged_attn_bf16": [vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                            i, i, i, i, i, i, f, i64, vp],
+        "swiglu_bf16": [vp, vp, i, i, vp],
+        "argmax_bf16": [vp, vp, i, i, vp, vp, i, vp],
+        "decode_attn_bf16": [vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                             i, i, i, i, i, f, i64, i, i, i, vp, i, vp],
+        "rope_append_bf16": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                             i, i, i, i, i, i, i64, i64, i64, vp],
+        "prefill_attn_bf16": [vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                              i, i, i, i, i, f, i64, i, vp],
+        "embed_gather_bf16": [vp, vp, vp, i, i, vp],
+        "wstream_gemm_bf16": [vp, vp, vp, vp, vp, i, i, i, i64, i,
+                              i, i, vp, i, f, f, vp, vp, i, vp],
+        "wstream_pure_bf16": [vp, vp, i, i, i, vp],
+        "wstream_gu_bf16": [vp, vp, vp, i, i, i, i64, i,
+                            vp, i, f, f, i, vp],
+        "row_sumsq_bf16": [vp, vp, i, i, vp],
+        "fragify_sumsq_bf16": [vp, vp, vp, i, i, vp],
+        "sample_gumbel_bf16": [vp, vp, vp, vp, vp, vp, i, i,
+                               vp, vp, i, vp],
+        "decode_pure_bf16": [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp],
+        "wstream_qkv_rope_bf16": [vp, vp, vp, vp, i, i, i, i64,
+                                  vp, i, f, f, vp, vp, vp, vp,
+                                  vp, vp, vp, i, i, i, i, i, vp],
+    }
+
+
 def _try_load():
     global _lib, _load_err
     if _lib is not None or _load_err is not None:
@@ -34,47 +70,10 @@ def _try_load():
     except OSError as e:
         _load_err = f"cannot load {_LIB_PATH}: {e}"
         return
-    vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    lib.rmsnorm_residual_bf16.argtypes = [vp, vp, vp, vp, vp, i, i, f, vp]
-    i64 = ctypes.c_int64
-    lib.rope_bf16.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i64, i64, vp]
-    lib.kv_append_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp,
-                                   i, i, i, i, i, i64, vp]
-    lib.paged_attn_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                    i, i, i, i, i, i, f, i64, vp]
-    lib.swiglu_bf16.argtypes = [vp, vp, i, i, vp]
-    lib.argmax_bf16.argtypes = [vp, vp, i, i, vp, vp, i, vp]
-    lib.decode_attn_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                     i, i, i, i, i, f, i64, i, i, i, vp,
-                                     i, vp]
-    lib.skinny_gemm_bf16.argtypes = [vp, vp, vp, vp, i, i, i, i64, i, vp]
-    lib.skinny_direct_bf16.argtypes = [vp, vp, vp, vp, i, i, i, i64, i, vp]
-    lib.rope_append_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                     i, i, i, i, i, i, i64, i64, i64, vp]
-    lib.prefill_attn_bf16.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp,
-                                      i, i, i, i, i, f, i64, i, vp]
-    lib.embed_gather_bf16.argtypes = [vp, vp, vp, i, i, vp]
-    lib.wstream_gemm_bf16.argtypes = [vp, vp, vp, vp, vp, i, i, i, i64, i,
-                                      i, i, vp, i, f, f, vp, vp, i, vp]
-    lib.wstream_pure_bf16.argtypes = [vp, vp, i, i, i, vp]
-    lib.wstream_gu_bf16.argtypes = [vp, vp, vp, i, i, i, i64, i,
-                                    vp, i, f, f, i, vp]
-    lib.row_sumsq_bf16.argtypes = [vp, vp, i, i, vp]
-    lib.fragify_sumsq_bf16.argtypes = [vp, vp, vp, i, i, vp]
-    lib.sample_gumbel_bf16.argtypes = [vp, vp, vp, vp, vp, vp, i, i,
-                                       vp, vp, i, vp]
-    lib.decode_pure_bf16.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i,
-                                     i, i, vp]
-    lib.wstream_qkv_rope_bf16.argtypes = [vp, vp, vp, vp, i, i, i, i64,
-                                          vp, i, f, f, vp, vp, vp, vp,
-                                          vp, vp, vp, i, i, i, i, i, vp]
-    for fn in ("rmsnorm_residual_bf16", "rope_bf16", "kv_append_bf16",
-               "paged_attn_bf16", "swiglu_bf16", "argmax_bf16",
-               "decode_attn_bf16", "skinny_gemm_bf16",
-               "skinny_direct_bf16", "prefill_attn_bf16",
-               "rope_append_bf16", "embed_gather_bf16",
-               "wstream_gemm_bf16"):
-        getattr(lib, fn).restype = ctypes.c_int
+    for name, argtypes in _signatures().items():
+        fn = getattr(lib, name)
+        fn.argtypes = argtypes
+        fn.restype = ctypes.c_int       # every entry point returns hipError
     _lib = lib
 
 
@@ -106,6 +105,28 @@ def _p(t: Optional[torch.Tensor]):
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
 
 
+def _i32(t: torch.Tensor):
+    """The kernels index with int32: convert only when needed.  Bind the
+    result to a local for the launch — a temporary would be freed (and
+    its block reused) before the kernel reads it."""
+    return t if t.dtype == torch.int32 else t.int()
+
+
+# Process-lifetime scratch buffers, allocated on first use and shared by
+# every later call with the same key.  A buffer first allocated INSIDE a
+# hipGraph capture would live in that graph's private pool while other
+# graphs and eager code reuse it, so the pre-capture eager warm-up must
+# be the first caller of every key (NOTES.md, graph-capture hygiene).
+_scratch = {}
+
+
+def _cached(key, make):
+    t = _scratch.get(key)
+    if t is None:
+        t = _scratch[key] = make()
+    return t
+
+
 # ---------------------------------------------------------------------------
 
 def embedding(tokens, table):
@@ -114,7 +135,7 @@ def embedding(tokens, table):
     V, H = table.shape
     if H % 8 or table.dtype != torch.bfloat16:
         return table.index_select(0, tokens.long())
-    tok32 = tokens if tokens.dtype == torch.int32 else tokens.int()
+    tok32 = _i32(tokens)
     out = torch.empty((T, H), dtype=table.dtype, device=table.device)
     _check(_lib.embed_gather_bf16(_p(out), _p(table), _p(tok32), T, H,
                                   _stream()), "embed_gather")
@@ -152,7 +173,7 @@ def rope(q, k, positions, cos, sin):
     T, Hq, D = q.shape
     Hk = k.shape[1]
     assert D == 128, "rope kernel specialized for head_dim=128"
-    pos32 = positions if positions.dtype == torch.int32 else positions.int()
+    pos32 = _i32(positions)
     _check(_lib.rope_bf16(_p(q), _p(k), _p(pos32), _p(cos), _p(sin),
                           T, Hq, Hk, D, _row_stride(q, D), _row_stride(k, D),
                           _stream()), "rope")
@@ -161,8 +182,7 @@ def rope(q, k, positions, cos, sin):
 def kv_append(cache, layer, k, v, slot_ids, positions):
     T, KVH, D = k.shape
     kp, vp = _layer_ptrs(cache, layer)
-    pos32 = positions if positions.dtype == torch.int32 else positions.int()
-    slot32 = slot_ids if slot_ids.dtype == torch.int32 else slot_ids.int()
+    pos32, slot32 = _i32(positions), _i32(slot_ids)
     assert _row_stride(k, D) == _row_stride(v, D)
     _check(_lib.kv_append_bf16(kp, vp, _p(k), _p(v), _p(slot32), _p(pos32),
                                _p(cache.page_table), T, KVH, D,
@@ -176,8 +196,7 @@ def rope_append(cache, layer, q, k, v, positions, slot_ids, cos, sin):
     KVH = k.shape[1]
     assert D == 128
     kp, vp = _layer_ptrs(cache, layer)
-    pos32 = positions if positions.dtype == torch.int32 else positions.int()
-    slot32 = slot_ids if slot_ids.dtype == torch.int32 else slot_ids.int()
+    pos32, slot32 = _i32(positions), _i32(slot_ids)
     _check(_lib.rope_append_bf16(
         _p(q), _p(k), _p(v), kp, vp, _p(pos32), _p(slot32),
         _p(cache.page_table), _p(cos), _p(sin), T, Hq, KVH, D,
@@ -195,6 +214,24 @@ def _layer_ptrs(cache, layer):
 PREFILL_QT = 32
 
 
+def _tile_plan(slot_ids, seq_lens, cu_q, qt):
+    """Cut each sequence's new query rows into tiles of at most qt rows.
+    Returns int32 device arrays (slot, first flat q row, absolute position
+    of that row, rows in tile); cu_q holds absolute flat row offsets."""
+    slots, lens, cu = slot_ids.tolist(), seq_lens.tolist(), cu_q.tolist()
+    ts, tq, tp, tr = [], [], [], []
+    for i, slot in enumerate(slots):
+        qlen = cu[i + 1] - cu[i]
+        start_pos = lens[i] - qlen
+        for t0 in range(0, qlen, qt):
+            ts.append(slot)
+            tq.append(cu[i] + t0)
+            tp.append(start_pos + t0)
+            tr.append(min(qt, qlen - t0))
+    return tuple(torch.tensor(a, dtype=torch.int32, device=slot_ids.device)
+                 for a in (ts, tq, tp, tr))
+
+
 def _attn_plan(cache, meta, qt):
     """Device tile arrays for the attention launch, cached on the meta
     object (one build per forward, shared by every layer)."""
@@ -202,34 +239,33 @@ def _attn_plan(cache, meta, qt):
     plan = getattr(meta, key, None)
     if plan is not None:
         return plan
-    dev = meta.slot_ids.device
     if qt == 1:
+        dev = meta.slot_ids.device
         n = meta.slot_ids.shape[0]
-        tile_slot = meta.slot_ids.int()
-        tile_q0 = torch.arange(n, dtype=torch.int32, device=dev)
-        tile_pos0 = (meta.seq_lens - 1).int()
-        tile_rows = torch.ones(n, dtype=torch.int32, device=dev)
+        plan = (meta.slot_ids.int(),
+                torch.arange(n, dtype=torch.int32, device=dev),
+                (meta.seq_lens - 1).int(),
+                torch.ones(n, dtype=torch.int32, device=dev))
     else:
-        slots = meta.slot_ids.tolist()
-        lens = meta.seq_lens.tolist()
-        cu = meta.cu_q.tolist()
-        ts, tq, tp, tr = [], [], [], []
-        for i, slot in enumerate(slots):
-            qlen = cu[i + 1] - cu[i]
-            start_pos = lens[i] - qlen
-            for t0 in range(0, qlen, qt):
-                rows = min(qt, qlen - t0)
-                ts.append(slot)
-                tq.append(cu[i] + t0)
-                tp.append(start_pos + t0)
-                tr.append(rows)
-        tile_slot = torch.tensor(ts, dtype=torch.int32, device=dev)
-        tile_q0 = torch.tensor(tq, dtype=torch.int32, device=dev)
-        tile_pos0 = torch.tensor(tp, dtype=torch.int32, device=dev)
-        tile_rows = torch.tensor(tr, dtype=torch.int32, device=dev)
-    plan = (tile_slot, tile_q0, tile_pos0, tile_rows)
+        plan = _tile_plan(meta.slot_ids, meta.seq_lens, meta.cu_q, qt)
     setattr(meta, key, plan)
     return plan
+
+
+def _prefill_launch(out, q, cache, layer, plan, window):
+    """prefill_attn_bf16 over a tile plan; writes the tiles' rows of out."""
+    T, Hq, D = q.shape
+    tile_slot, tile_q0, tile_pos0, tile_rows = plan
+    n_tiles = tile_slot.shape[0]
+    if n_tiles == 0:
+        return
+    kp, vp = _layer_ptrs(cache, layer)
+    _check(_lib.prefill_attn_bf16(
+        _p(out), _p(q), kp, vp, _p(cache.page_table),
+        _p(tile_slot), _p(tile_q0), _p(tile_pos0), _p(tile_rows),
+        n_tiles, Hq, cache.n_kv_heads, cache.page_size,
+        cache.page_table.shape[1], 1.0 / (D ** 0.5), _row_stride(q, D),
+        window, _stream()), "prefill_attn")
 
 
 def _attention(q, cache, layer, meta, qt):
@@ -250,31 +286,33 @@ def _attention(q, cache, layer, meta, qt):
     return out
 
 
-_scratch = {}
-
-
 def _decode_scratch(S, Hq, split, dev):
-    key = (S, Hq, split, str(dev))
-    t = _scratch.get(key)
-    if t is None:
-        t = (torch.empty(S * Hq * split * 128, dtype=torch.float32,
-                         device=dev),
-             torch.empty(S * Hq * split * 2, dtype=torch.float32,
-                         device=dev))
-        _scratch[key] = t
-    return t
+    """(o_part, ml_part) fp32 partials of the KV-split decode attention."""
+    return _cached((S, Hq, split, str(dev)), lambda: (
+        torch.empty(S * Hq * split * 128, dtype=torch.float32, device=dev),
+        torch.empty(S * Hq * split * 2, dtype=torch.float32, device=dev)))
 
 
 def _combine_sem(S, KVH, dev):
     """Ticket counters for the in-launch split-K combine: zero-initialized
     once; the last-arriving block resets its counter, so the buffer is
     always all-zero between launches (guide G16 counter recipe)."""
-    key = ("sem", S, KVH, str(dev))
-    t = _scratch.get(key)
-    if t is None:
-        t = torch.zeros(S * KVH, dtype=torch.int32, device=dev)
-        _scratch[key] = t
-    return t
+    return _cached(("sem", S, KVH, str(dev)), lambda: torch.zeros(
+        S * KVH, dtype=torch.int32, device=dev))
+
+
+def _splitv_scratch(tag, B, device):
+    """Split-V factor and (value, index) partial buffers shared by the
+    argmax and Gumbel samplers: B blocks alone underfill the chip at
+    decode batch sizes, so each row is scanned by sp blocks.  Returns
+    (sp, pb, pi); null pointers when sp == 1."""
+    sp = min(32, max(1, 768 // max(1, B)))
+    if sp == 1:
+        return sp, ctypes.c_void_p(0), ctypes.c_void_p(0)
+    pb, pi = _cached((tag, B, sp, str(device)), lambda: (
+        torch.empty(B * sp, dtype=torch.float32, device=device),
+        torch.empty(B * sp, dtype=torch.int32, device=device)))
+    return sp, _p(pb), _p(pi)
 
 
 # staged KV chunk length (tokens) per pipeline stage; 32/64 compiled
@@ -328,10 +366,7 @@ def attention_decode(q, cache, layer, meta, fragout=False):
         # fewer, longer blocks.
         if os.environ.get("OLLAMAMQ_FUSED_COMBINE") == "1":
             sem = _p(_combine_sem(S, kvh, q.device))
-    slot32 = meta.slot_ids.int() if meta.slot_ids.dtype != torch.int32 \
-        else meta.slot_ids
-    len32 = meta.seq_lens.int() if meta.seq_lens.dtype != torch.int32 \
-        else meta.seq_lens
+    slot32, len32 = _i32(meta.slot_ids), _i32(meta.seq_lens)
     _check(_lib.decode_attn_bf16(
         _p(out), op, mp, _p(q), kp, vp, _p(cache.page_table),
         _p(slot32), _p(len32), S, Hq, kvh, cache.page_size,
@@ -363,34 +398,10 @@ def attention_mixed(q, cache, layer, meta):
     # ---- prefill part (tiles over sequences nd..) ----
     plan = getattr(meta, "_mixed_plan", None)
     if plan is None:
-        slots = meta.slot_ids[nd:].tolist()
-        lens = meta.seq_lens[nd:].tolist()
-        cu = meta.cu_q[nd:].tolist()
-        dev = q.device
-        ts, tq, tp, tr = [], [], [], []
-        for i, slot in enumerate(slots):
-            qlen = cu[i + 1] - cu[i]
-            start_pos = lens[i] - qlen
-            for t0 in range(0, qlen, PREFILL_QT):
-                ts.append(slot)
-                tq.append(cu[i] + t0)
-                tp.append(start_pos + t0)
-                tr.append(min(PREFILL_QT, qlen - t0))
-        plan = (torch.tensor(ts, dtype=torch.int32, device=dev),
-                torch.tensor(tq, dtype=torch.int32, device=dev),
-                torch.tensor(tp, dtype=torch.int32, device=dev),
-                torch.tensor(tr, dtype=torch.int32, device=dev))
+        plan = _tile_plan(meta.slot_ids[nd:], meta.seq_lens[nd:],
+                          meta.cu_q[nd:], PREFILL_QT)
         meta._mixed_plan = plan
-    tile_slot, tile_q0, tile_pos0, tile_rows = plan
-    n_tiles = tile_slot.shape[0]
-    if n_tiles:
-        kp, vp = _layer_ptrs(cache, layer)
-        _check(_lib.prefill_attn_bf16(
-            _p(out), _p(q), kp, vp, _p(cache.page_table),
-            _p(tile_slot), _p(tile_q0), _p(tile_pos0), _p(tile_rows),
-            n_tiles, Hq, cache.n_kv_heads, cache.page_size,
-            cache.page_table.shape[1], 1.0 / (D ** 0.5),
-            _row_stride(q, D), meta.window, _stream()), "prefill_attn")
+    _prefill_launch(out, q, cache, layer, plan, meta.window)
     return out
 
 
@@ -403,48 +414,17 @@ def attention_prefill(q, cache, layer, meta):
     T, Hq, D = q.shape
     assert D == 128
     out = torch.empty((T, Hq, D), dtype=q.dtype, device=q.device)
-    kp, vp = _layer_ptrs(cache, layer)
-    tile_slot, tile_q0, tile_pos0, tile_rows = _attn_plan(cache, meta,
-                                                          PREFILL_QT)
-    n_tiles = tile_slot.shape[0]
-    if n_tiles == 0:
-        return out
-    _check(_lib.prefill_attn_bf16(
-        _p(out), _p(q), kp, vp, _p(cache.page_table),
-        _p(tile_slot), _p(tile_q0), _p(tile_pos0), _p(tile_rows),
-        n_tiles, Hq, cache.n_kv_heads, cache.page_size,
-        cache.page_table.shape[1], 1.0 / (D ** 0.5), _row_stride(q, D),
-        meta.window, _stream()), "prefill_attn")
+    _prefill_launch(out, q, cache, layer,
+                    _attn_plan(cache, meta, PREFILL_QT), meta.window)
     return out
-
-
-# default 0 = library GEMMs everywhere: the fragment-direct kernel beats
-# hipBLASLt on qkv/o in MICROBENCHES (L3-warm weights re-read 100x) but
-# loses ~0.3 ms/step in the real serving loop where weights stream cold
-# from HBM — honest A/B in bench.py decided this (5473 vs 5221 tok/s).
-# The hand-written variants stay available via these env gates.
-SKINNY_MAX_N = int(os.environ.get("OLLAMAMQ_SKINNY_MAX_N", "0"))
-SKINNY_MAX_K = int(os.environ.get("OLLAMAMQ_SKINNY_MAX_K", "0"))
-
-_gemm_scratch = {}
-
-
-def _skinny_ksplit(N, K):
-    """grid k-split: target >=768 blocks (~3/CU) so independent blocks
-    hide each other's staging latency; kseg must stay a multiple of 256
-    (even chunk count for the 2-deep pipeline)."""
-    blocks = N // 32
-    ks = 1
-    while blocks * ks < 768 and ks < 8 and K % (256 * 2 * ks) == 0:
-        ks *= 2
-    return ks
 
 
 def pack_weight(w):
     """Pre-pack a [N, K] bf16 weight into MFMA fragment order for the
-    weight-streaming decode GEMM (wstream_gemm.hip): element W[n][k] with
-    n = t*32+r, k = b*64 + j*16 + h*8 + e goes to 16-byte unit
-    ((t*NB + b)*4 + j)*64 + (h*32 + r).  The kernel's loads then walk the
+    weight-streaming decode GEMM (wstream_gemm.hip): each 32-row tile in
+    the frag layout of csrc/kernels/common.cuh, which the reshape below
+    spells (t, r, b, j, h, e) -> (t, b, j, h, r, e) for n = t*32 + r,
+    k = b*64 + j*16 + h*8 + e.  The kernel's loads then walk the
     buffer LINEARLY (full 128 B line per instruction, nt-tagged) — the fix
     for the 4x cold-line over-fetch of fragment-direct loads (NOTES r01).
     Returns None when the shape doesn't qualify."""
@@ -539,8 +519,7 @@ def linear_qkv_rope(x, packed, N, bias_rp, cache, layer, positions,
         M, xs, xf = M_real, 0, 1
     y = torch.empty((M, N), dtype=x.dtype, device=x.device)
     kp, vp = _layer_ptrs(cache, layer)
-    pos32 = positions if positions.dtype == torch.int32 else positions.int()
-    slot32 = slots if slots.dtype == torch.int32 else slots.int()
+    pos32, slot32 = _i32(positions), _i32(slots)
     _check(_lib.wstream_qkv_rope_bf16(
         _p(y), _p(x), _p(packed), _p(bias_rp), M, N, K, xs,
         _p(rstd), rstd_nt, float(inv_h), float(eps),
@@ -641,13 +620,9 @@ def linear_packed(x, packed, bias, N, ks=None, depth=None, xlds=None,
                          "epilogue)")
     part = ctypes.c_void_p(0)
     if ks > 1:
-        key = ("ws", M, N, ks, str(x.device))
-        t = _gemm_scratch.get(key)
-        if t is None:
-            t = torch.empty(ks * M * N, dtype=torch.float32,
-                            device=x.device)
-            _gemm_scratch[key] = t
-        part = _p(t)
+        part = _p(_cached(("ws", M, N, ks, str(x.device)),
+                          lambda: torch.empty(ks * M * N, dtype=torch.float32,
+                                              device=x.device)))
     if xlds is None:
         # measured (profiles/r02_gemm_sweep.md): LDS x-staging pays on
         # long streams (down/gate_up/logits), the direct fragment load
@@ -700,37 +675,7 @@ def linear(x, weight, bias=None, packed=None):
             and (N <= _WS_MAX_N or N >= 65536) \
             and x.dtype == torch.bfloat16 and x.stride(1) == 1:
         return linear_packed(x, packed, bias, N)
-    # gated to the shapes where the hand-written kernel beats hipBLASLt
-    # (measured tools/perf_gemm.py); widen via env as the kernel improves
-    if bias is None and M <= 32 and K % 256 == 0 and N % 32 == 0 \
-            and N <= SKINNY_MAX_N and K <= SKINNY_MAX_K \
-            and x.dtype == torch.bfloat16 and weight.stride(1) == 1:
-        y = torch.empty((M, N), dtype=x.dtype, device=x.device)
-        assert x.stride(1) == 1
-        direct = os.environ.get("OLLAMAMQ_SKINNY_STAGED") != "1"
-        if direct:
-            # per-wave k extent must be a multiple of 64
-            ks = 1
-            blocks = N // 32
-            while blocks * ks < 768 and ks < 8 and K % (ks * 2 * 512) == 0:
-                ks *= 2
-            if K % (ks * 512) != 0:
-                return torch.nn.functional.linear(x, weight)
-        else:
-            ks = _skinny_ksplit(N, K)
-        part = ctypes.c_void_p(0)
-        if ks > 1:
-            key = (M, N, ks, str(x.device))
-            t = _gemm_scratch.get(key)
-            if t is None:
-                t = torch.empty(ks * M * N, dtype=torch.float32,
-                                device=x.device)
-                _gemm_scratch[key] = t
-            part = _p(t)
-        fn = _lib.skinny_direct_bf16 if direct else _lib.skinny_gemm_bf16
-        _check(fn(_p(y), part, _p(x), _p(weight),
-                  M, N, K, x.stride(0), ks, _stream()), "skinny_gemm")
-        return y
+    # everything else (no pack, M > 64, N past _WS_MAX_N): library GEMM
     return torch.nn.functional.linear(x, weight, bias)
 
 
@@ -755,18 +700,7 @@ def sample_gumbel(logits, temps, seeds, ctrs, noise=None, out=None):
     l = logits if logits.dtype == torch.bfloat16 else logits.bfloat16()
     if out is None:
         out = torch.empty(B, dtype=torch.int32, device=logits.device)
-    sp = min(32, max(1, 768 // max(1, B)))
-    pb = pi = ctypes.c_void_p(0)
-    if sp > 1:
-        key = ("gmb", B, sp, str(logits.device))
-        t = _scratch.get(key)
-        if t is None:
-            t = (torch.empty(B * sp, dtype=torch.float32,
-                             device=logits.device),
-                 torch.empty(B * sp, dtype=torch.int32,
-                             device=logits.device))
-            _scratch[key] = t
-        pb, pi = _p(t[0]), _p(t[1])
+    sp, pb, pi = _splitv_scratch("gmb", B, logits.device)
     _check(_lib.sample_gumbel_bf16(
         _p(out), _p(l), _p(temps), _p(seeds), _p(ctrs), _p(noise),
         B, V, pb, pi, sp, _stream()), "sample_gumbel")
@@ -782,19 +716,7 @@ def sample(logits, temperature, top_k, top_p, generator=None):
         B, V = logits.shape
         out = torch.empty(B, dtype=torch.int32, device=logits.device)
         l = logits if logits.dtype == torch.bfloat16 else logits.bfloat16()
-        # split-V: B blocks alone underfill the chip at decode batch sizes
-        sp = min(32, max(1, 768 // max(1, B)))
-        pb = pi = ctypes.c_void_p(0)
-        if sp > 1:
-            key = ("amax", B, sp, str(logits.device))
-            t = _scratch.get(key)
-            if t is None:
-                t = (torch.empty(B * sp, dtype=torch.float32,
-                                 device=logits.device),
-                     torch.empty(B * sp, dtype=torch.int32,
-                                 device=logits.device))
-                _scratch[key] = t
-            pb, pi = _p(t[0]), _p(t[1])
+        sp, pb, pi = _splitv_scratch("amax", B, logits.device)
         _check(_lib.argmax_bf16(_p(out), _p(l), B, V, pb, pi, sp,
                                 _stream()), "argmax")
         return out.long()
@@ -846,9 +768,10 @@ def decode_pure(cache, layer, meta, split, chunk=64):
     sink = torch.zeros(1, dtype=torch.float32, device=cache.k_pool.device)
     kp, vp = _layer_ptrs(cache, layer)
     S = meta.slot_ids.shape[0]
+    slot32, len32 = _i32(meta.slot_ids), _i32(meta.seq_lens)
     _check(_lib.decode_pure_bf16(
-        _p(sink), kp, vp, _p(cache.page_table), _p(meta.slot_ids.int()),
-        _p(meta.seq_lens.int()), S, cache.n_kv_heads, cache.page_size,
+        _p(sink), kp, vp, _p(cache.page_table), _p(slot32),
+        _p(len32), S, cache.n_kv_heads, cache.page_size,
         cache.page_table.shape[1], split, chunk, _stream()),
         "decode_pure")
     return sink

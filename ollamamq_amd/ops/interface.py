@@ -157,7 +157,8 @@ def pack_weight_gu(w):
 
 
 # ---- fused-rmsnorm decode chain (GPU-only; the model gates on
-# fused_chain availability — tp=1, decode, batch<=32) -----------------
+# fused_chain availability — tp=1, decode, batch<=64: rows 33..64 ride
+# the MT=2 frag kernels over two 32-row frag buffers) ------------------
 
 def row_sumsq(x, out=None):
     """sq[m] = sum(x[m]**2) in fp32 (seeds the chain after embedding)."""

@@ -12,7 +12,7 @@ from ollamamq_amd.ops import hip
 
 
 def _frag_off(m, kcol):
-    """Scalar transcription of frag_off() in wstream_gemm.hip."""
+    """Scalar transcription of frag_off() in csrc/kernels/common.cuh."""
     b, j, h = kcol >> 6, (kcol >> 4) & 3, (kcol >> 3) & 1
     return (((b * 4 + j) * 64) + h * 32 + m) * 8 + (kcol & 7)
 

@@ -1,12 +1,13 @@
-"""Skinny MFMA GEMM vs torch matmul (asymmetric random inputs — catches
-operand/output transposes, guide §5.4 rule 16)."""
+"""hip.linear without a packed weight: falls through to the library GEMM,
+strided rows included, vs torch matmul in fp32 (asymmetric random inputs —
+catches operand/output transposes, guide §5.4 rule 16)."""
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
 
-def test_skinny_gemm_matches_torch():
+def test_linear_unpacked_matches_torch():
     from ollamamq_amd.ops import hip
     hip.require()
     g = torch.Generator().manual_seed(5)
@@ -23,7 +24,7 @@ def test_skinny_gemm_matches_torch():
         torch.testing.assert_close(y.float(), y_ref, atol=0.5, rtol=2e-2)
 
 
-def test_skinny_gemm_strided_x():
+def test_linear_unpacked_strided_x():
     from ollamamq_amd.ops import hip
     hip.require()
     g = torch.Generator().manual_seed(6)
