@@ -9,9 +9,21 @@ GEMM dispatch) within bf16 tolerance.
 import pytest
 import torch
 
+import model_oracle as mo
+
 pytestmark = pytest.mark.gpu
 
 PROMPT = [3, 1, 4, 1, 5, 9, 2, 6, 5, 3]
+
+
+def _hold_to_oracle(seqs, lg, lf):
+    """Both paths' logits rows (the last position of each full token
+    sequence) within the measured budget of tests/model_oracle.py."""
+    assert mo.SEED == 1234       # the seed _mk builds its model with
+    truth, budget = mo.truth_and_budget(mo.cpu_model("tiny"), seqs)
+    want = torch.stack([l[-1] for l in truth.logits])
+    budget.hold("logits", lg, want, "generic path")
+    budget.hold("logits", lf, want, "fused chain")
 
 
 def _mk(model_name="tiny", batch=4):
@@ -59,7 +71,7 @@ def test_fused_chain_logits_close():
     B = 5
     dev = "cuda:0"
     g = torch.Generator().manual_seed(7)
-    slots = []
+    slots, seqs = [], []
     # seed some KV context per slot
     for s in range(B):
         slot = kv.alloc_slot()
@@ -68,6 +80,7 @@ def test_fused_chain_logits_close():
         kv.ensure(slot, L)
         toks = torch.randint(0, cfg.vocab, (L,), generator=g,
                              dtype=torch.int32).to(dev)
+        seqs.append(toks.tolist())
         pos = torch.arange(L, dtype=torch.int32, device=dev)
         st = torch.full((L,), slot, dtype=torch.int32, device=dev)
         meta = AttnMeta(mode="prefill",
@@ -112,6 +125,7 @@ def test_fused_chain_logits_close():
     torch.testing.assert_close(lf.float(), lg.float(), atol=1e-1,
                                rtol=1e-1)
     assert torch.equal(lf.argmax(-1), lg.argmax(-1))
+    _hold_to_oracle([c + [t] for c, t in zip(seqs, toks.tolist())], lg, lf)
 
 
 @pytest.mark.parametrize("B", [33, 64])
@@ -123,7 +137,7 @@ def test_fused_chain_mt2_single_forward_rows(B):
     cfg, model, kv = _mk(batch=B)
     dev = "cuda:0"
     g = torch.Generator().manual_seed(11)
-    slots = []
+    slots, seqs = [], []
     for s in range(B):
         slot = kv.alloc_slot()
         slots.append(slot)
@@ -131,6 +145,7 @@ def test_fused_chain_mt2_single_forward_rows(B):
         kv.ensure(slot, L)
         toks = torch.randint(0, cfg.vocab, (L,), generator=g,
                              dtype=torch.int32).to(dev)
+        seqs.append(toks.tolist())
         pos = torch.arange(L, dtype=torch.int32, device=dev)
         st = torch.full((L,), slot, dtype=torch.int32, device=dev)
         one = torch.tensor([slot], dtype=torch.int32, device=dev)
@@ -176,6 +191,7 @@ def test_fused_chain_mt2_single_forward_rows(B):
     top2 = lg.topk(2, dim=-1).values
     clear = (top2[:, 0] - top2[:, 1]) > 2 * atol
     assert torch.equal(lf.argmax(-1)[clear], lg.argmax(-1)[clear])
+    _hold_to_oracle([c + [t] for c, t in zip(seqs, toks.tolist())], lg, lf)
 
 
 def test_fused_chain_mt2_batch_over_32():

@@ -20,6 +20,7 @@ pytestmark = pytest.mark.gpu
 import attn_oracle as ao
 import elem_oracle as eo
 import fused_oracle as fo
+import model_oracle as mo
 from ollamamq_amd.ops import reference as ref
 from ollamamq_amd.engine.kvcache import PagedKVCache
 from ollamamq_amd.ops.interface import AttnMeta
@@ -214,7 +215,9 @@ def test_attention_prefill_sliding_window():
 @pytest.mark.parametrize("preset", ["tiny-qwen", "tiny-swa"])
 def test_family_forward_gpu_vs_cpu(preset):
     """Qwen2-bias / Mistral-window variants end to end on the HIP path:
-    greedy tokens from a long prompt must track the CPU fp32 engine."""
+    greedy tokens from a long prompt must track the CPU fp32 engine, and
+    each of the 8 must be near the fp64 oracle's best at the prefix the
+    GPU actually had (tests/model_oracle.py trajectory check)."""
     from ollamamq_amd.models import LlamaModel, PRESETS
     from ollamamq_amd.engine import LlamaEngine, PagedKVCache, GenParams
     cfg = PRESETS[preset]
@@ -239,6 +242,11 @@ def test_family_forward_gpu_vs_cpu(preset):
     assert len(gpu) == len(cpu) == 8
     # greedy ties can flip late under bf16; the first tokens must agree
     assert gpu[:2] == cpu[:2], f"{gpu} vs {cpu}"
+    truth, budget = mo.truth_and_budget(
+        mo.cpu_model(preset, torch.bfloat16, 11), [prompt + gpu])
+    for k, t in enumerate(gpu):
+        assert mo.greedy_ok(truth.logits[0][len(prompt) + k - 1], t,
+                            budget.logits_mx), f"token {k} of {gpu}"
 
 
 def test_attention_prefill_odd_gqa_group():
@@ -296,7 +304,9 @@ def test_argmax_sampler():
 
 def test_forward_e2e_vs_cpu():
     """Whole tiny-model forward GPU-bf16 vs CPU-fp32: logits must agree to
-    bf16 tolerance (cosine > 0.995 per row)."""
+    bf16 tolerance (cosine > 0.995 per row), and EVERY captured step's
+    logits rows must stay within the measured budget of the fp64 oracle
+    run on the tokens the GPU consumed (tests/model_oracle.py)."""
     from ollamamq_amd.models import LlamaModel, PRESETS
     from ollamamq_amd.engine import LlamaEngine, PagedKVCache, GenParams
     cfg = PRESETS["tiny"]
@@ -310,13 +320,18 @@ def test_forward_e2e_vs_cpu():
         # test captures logits through _sample, so use the plain path
         # (pipelined-vs-plain equivalence is covered by test_pipeline_gpu)
         eng.use_pipeline = False
-        eng.submit(list(range(1, 33)), GenParams(max_tokens=4))
-        eng.submit(list(range(40, 52)), GenParams(max_tokens=4))
-        logits_log = []
+        submitted = [
+            eng.seqs[eng.submit(list(range(1, 33)), GenParams(max_tokens=4))],
+            eng.seqs[eng.submit(list(range(40, 52)),
+                                GenParams(max_tokens=4))]]
+        logits_log, rows_log = [], []
         orig_sample = eng._sample
 
         def capture(seqs, logits):
             logits_log.append(logits.float().cpu())
+            # row i holds the logits after seqs[i]'s last token so far
+            rows_log.append([(submitted.index(s), s.total_len - 1)
+                             for s in seqs])
             return orig_sample(seqs, logits)
 
         eng._sample = capture
@@ -324,16 +339,24 @@ def test_forward_e2e_vs_cpu():
             eng.step()
             if not eng.has_work():
                 break
-        return logits_log
+        return logits_log, rows_log, [s.prompt + s.generated
+                                      for s in submitted]
 
-    gpu_logits = run(dev(), torch.bfloat16)
-    cpu_logits = run("cpu", torch.float32)
+    gpu_logits, gpu_rows, gpu_full = run(dev(), torch.bfloat16)
+    cpu_logits = run("cpu", torch.float32)[0]
     assert len(gpu_logits) == len(cpu_logits)
     # Step 0 (prefill logits) sees identical inputs on both paths; later
     # steps may legitimately diverge once a greedy tie flips a token.
     a, b = gpu_logits[0], cpu_logits[0]
     cos = torch.nn.functional.cosine_similarity(a, b, dim=-1)
     assert cos.min() > 0.995, f"prefill logits diverged: {cos.min()}"
+    # teacher forcing: all steps, not only step 0
+    truth, budget = mo.truth_and_budget(
+        mo.cpu_model("tiny", torch.bfloat16, 11), gpu_full)
+    assert len(gpu_logits) >= 4      # 4 tokens need 4 sampled steps
+    for step, (lg, rows) in enumerate(zip(gpu_logits, gpu_rows)):
+        want = torch.stack([truth.logits[i][p] for i, p in rows])
+        budget.hold("logits", lg, want, f"step {step}")
 
 
 def test_fused_rope_append():
