@@ -27,6 +27,32 @@ from ..ops import interface as ops
 from .kvcache import PagedKVCache
 
 
+_M64 = (1 << 64) - 1
+
+
+def normalize_seed(seed) -> int:
+    """Any Python int as a request seed: reduced mod 2^64."""
+    return int(seed) & _M64
+
+
+def _fmix64(k: int) -> int:
+    k ^= k >> 33
+    k = (k * 0xFF51AFD7ED558CCD) & _M64
+    k ^= k >> 33
+    k = (k * 0xC4CEB9FE1A85EC53) & _M64
+    return k ^ (k >> 33)
+
+
+def host_seed_key(seed: int, index: int) -> int:
+    """Generator key of the host sampler for (request seed, token index):
+    two chained 64-bit finalisers, so every bit of either input reaches
+    the key and no XOR of the two inputs cancels by construction; the
+    result is cut to 63 bits, the range torch's manual_seed takes."""
+    k = _fmix64((normalize_seed(seed) + 0x9E3779B97F4A7C15) & _M64)
+    k = _fmix64(k ^ ((int(index) & _M64) * 0xD1B54A32D192ED03 & _M64))
+    return k & 0x7FFFFFFFFFFFFFFF
+
+
 @dataclass
 class GenParams:
     max_tokens: int = 128
@@ -130,10 +156,16 @@ class LlamaEngine:
         # per-sequence noise seed for the in-graph Gumbel sampler:
         # request seed (reproducible regardless of batch composition,
         # the counter is the sequence's own length) or a per-sequence
-        # engine default (deterministic across TP ranks: sid matches)
-        seq.noise_seed = (int(params.seed) if params.seed is not None
-                          else (0x5EED0000 ^ (sid * 0x9E3779B1)) &
-                               0x7FFFFFFFFFFFFFFF)
+        # engine default (deterministic across TP ranks: sid matches).
+        # A request seed is any Python int: it is reduced mod 2^64 once,
+        # here; the kernel's int64 seed is that value reinterpreted as
+        # signed, the host generator key is host_seed_key(seed, index).
+        if params.seed is not None:
+            u = normalize_seed(params.seed)
+            seq.noise_seed = u - (1 << 64) if u >> 63 else u
+        else:
+            seq.noise_seed = ((0x5EED0000 ^ (sid * 0x9E3779B1))
+                              & 0x7FFFFFFFFFFFFFFF)
         self.seqs[sid] = seq
         self.waiting.append(seq)
         return sid
@@ -357,8 +389,8 @@ class LlamaEngine:
             p = s.params
             if p.seed is not None and p.temperature > 0:
                 g = torch.Generator(device=logits.device)
-                g.manual_seed((int(p.seed) << 20)
-                              ^ (len(s.generated) + len(s.prompt)))
+                g.manual_seed(host_seed_key(
+                    s.noise_seed, len(s.generated) + len(s.prompt)))
                 t = ops.sample(logits[i:i + 1],
                                torch.tensor([p.temperature],
                                             dtype=torch.float32,
@@ -404,7 +436,9 @@ class LlamaEngine:
 
     def _samp_class(self, seqs) -> int:
         """0 = all greedy (argmax tail), 1 = temperature-only mix (Gumbel
-        tail — exact), 2 = top-k/top-p present.
+        tail — exact), 2 = top-k/top-p present and every stochastic row
+        has 0 < top_k <= 256 (in-graph candidate tail — exact), 3 =
+        top-k/top-p present otherwise (host, exact).
 
         Class 2 is captured ONLY behind OLLAMAMQ_GRAPH_TOPK=1: the
         candidate tail (torch.topk over [B, 128256] + filters) is clean
@@ -414,14 +448,21 @@ class LlamaEngine:
         — an unresolved interaction between the captured topk and the
         serving graph set.  Until root-caused, top-k/p rows sample on the
         host (exact, full vocabulary) with the forward still graphed."""
-        k = 0
+        k, capped = 0, True
         for s in seqs:
             p = s.params
             if p.temperature > 0:
                 if (p.top_k or 0) > 0 or (p.top_p if p.top_p else 1.0) \
                         < 1.0:
-                    return 2 if self._GRAPH_TOPK else 3
-                k = 1
+                    k = 2
+                else:
+                    k = max(k, 1)
+                # the class-2 tail sees the top-256 candidates only: it
+                # is exact iff every stochastic row's support lies inside
+                # them (ops/hip.py sample: capped_ok)
+                capped &= 0 < (p.top_k or 0) <= 256
+        if k == 2:
+            return 2 if self._GRAPH_TOPK and capped else 3
         return k
 
     def _bucket(self, n: int) -> int:
@@ -511,8 +552,11 @@ class LlamaEngine:
         greedy rows ride the same kernel with T<=0), noise keyed by
         (per-seq seed, kv length) so replays draw fresh randomness with
         no host RNG; class 2 = per-row top-k/top-p over the top-256
-        candidates (capturable torch ops), then exact Gumbel-max on the
-        filtered set.
+        candidates with their full-vocabulary probabilities (capturable
+        torch ops; every stochastic row has 0 < top_k <= 256, see
+        _samp_class), then exact Gumbel-max on the filtered set, noise
+        keyed by the candidate's rank; greedy rows take the HIP argmax
+        of the full row.
 
         This MUST also run once EAGERLY in the pre-capture warmup: the
         samplers cache split-scratch buffers (ops/hip.py _scratch), and a
@@ -528,23 +572,31 @@ class LlamaEngine:
         if entry["klass"] == 2:
             from ..ops import hip as _hip
             C = min(256, logits.shape[1])
-            v, idx = torch.topk(logits.float(), C, dim=-1)
-            t = bufs["temps"].clamp(min=1e-6).unsqueeze(1)
-            p = torch.softmax(v / t, dim=-1)
+            lf = logits.float()
+            greedy = bufs["temps"] <= 0
+            t = torch.where(greedy, torch.ones_like(bufs["temps"]),
+                            bufs["temps"]).unsqueeze(1)
+            v, idx = torch.topk(lf, C, dim=-1)
+            # full-vocabulary logsumexp, as ops/hip.py sample: the
+            # top-p mass is measured on the true probabilities, not on
+            # the candidates renormalised
+            lse = torch.logsumexp(lf / t, dim=-1, keepdim=True)
+            p = torch.exp(v / t - lse)
             ar = torch.arange(C, device=logits.device)
-            kk = torch.where(bufs["topk"] > 0,
-                             bufs["topk"].clamp(max=C),
-                             torch.full_like(bufs["topk"], C))
-            keep = ar.unsqueeze(0) < kk.unsqueeze(1)
+            keep = ar.unsqueeze(0) < \
+                bufs["topk"].clamp(min=1, max=C).unsqueeze(1)
             cum = p.cumsum(dim=-1)
-            keep &= (cum - p) < bufs["topp"].unsqueeze(1)
+            tpc = bufs["topp"].unsqueeze(1)
+            keep &= ((cum - p) < tpc) | (tpc >= 1.0)
             keep[:, 0] = True
-            # greedy rows bypass the (garbage) filter math
-            keep |= (bufs["temps"] <= 0).unsqueeze(1)
             vm = v.masked_fill(~keep, float("-inf")).bfloat16()
             ci = _hip.sample_gumbel(vm.contiguous(), bufs["temps"],
                                     bufs["seeds"], bufs["lens"])
-            return idx.gather(1, ci.long().unsqueeze(1)).squeeze(1).int()
+            tok = idx.gather(1, ci.long().unsqueeze(1)).squeeze(1).int()
+            # greedy rows: the lowest-index maximum of the full row, as
+            # classes 0 and 1 (torch.topk promises no order among ties)
+            am = ops.sample(logits, 0.0, 0, 1.0, None).int()
+            return torch.where(greedy, am, tok)
         return ops.sample(logits, 0.0, 0, 1.0, None).int()
 
     def _graph_replay(self, entry):

@@ -750,7 +750,10 @@ def sample(logits, temperature, top_k, top_p, generator=None):
     ar = torch.arange(C, device=dev)
     keep = ar.unsqueeze(0) < tk.clamp(min=1, max=C).unsqueeze(1)
     cum = p.cumsum(dim=-1)
-    keep &= (cum - p) < tp.unsqueeze(1)
+    # top_p >= 1 is off (as ref.sample): at a low temperature the fp32
+    # cumsum is 1.0 from rank 0 on
+    tpc = tp.unsqueeze(1)
+    keep &= ((cum - p) < tpc) | (tpc >= 1.0)
     keep[:, 0] = True
     pm = p * keep
     pick = torch.multinomial(pm / pm.sum(-1, keepdim=True), 1,

@@ -150,7 +150,10 @@ def sample(logits, temperature, top_k, top_p, generator=None):
             kk = torch.where(tk > 0, tk.clamp(max=V), torch.full_like(tk, V))
             keep = ar.unsqueeze(0) < kk.unsqueeze(1)          # per-row top-k
             cum = sp.cumsum(dim=-1)
-            keep &= (cum - sp) < tp.unsqueeze(1)   # keep token crossing mass
+            # keep the token crossing the mass; top_p >= 1 is OFF, not a
+            # cut at 1.0: the fp32 cumsum reaches 1.0 before the last rank
+            tpc = tp.unsqueeze(1)
+            keep &= ((cum - sp) < tpc) | (tpc >= 1.0)
             keep[:, 0] = True                      # never empty a row
             sp = sp * keep
             sp = sp / sp.sum(dim=-1, keepdim=True)

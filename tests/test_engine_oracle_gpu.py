@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import model_oracle as mo
+import sampler_oracle as so
 
 pytestmark = pytest.mark.gpu
 
@@ -106,20 +107,22 @@ def _drive(eng, steps=400):
     torch.cuda.synchronize()
 
 
-def _check(name, tap, seqs, what):
-    """Teacher-forced check of a finished run.  Returns the worst logits
-    ratio."""
+def _check(name, tap, seqs, what, tail="gumbel"):
+    """Teacher-forced check of a finished run.  tail: what samples the
+    decode tokens of a stochastic sequence, the in-graph "gumbel" tail or
+    the "host" (whose draws the caller checks).  Returns the oracle's
+    truth and budget."""
     full = [s.prompt + s.generated for s in seqs]
     truth, budget = mo.truth_and_budget(mo.cpu_model(name), full)
     index = {s.seq_id: i for i, s in enumerate(seqs)}
-    got, want, seen = [], [], set()
+    got, want, seen = [], [], {}
     for sid, p, row in tap.events:
         i = index[sid]
         if p >= len(full[i]):
             continue    # pipelined: one replay past the last kept token
         got.append(row)
         want.append(truth.logits[i][p])
-        seen.add((i, p))
+        seen[(i, p)] = row
     # every emitted token's logits row was recorded
     for i, s in enumerate(seqs):
         assert len(s.generated) >= 20, (what, len(s.generated))
@@ -137,7 +140,17 @@ def _check(name, tap, seqs, what):
             if T <= 0:
                 assert mo.greedy_ok(L, t, budget.logits_mx), \
                     f"{what}: seq {i} token {k} is not near the oracle's best"
-            elif k >= 1:
+            elif k == 0:
+                # sampled on the host from the row recorded at the end of
+                # the prefill: exact on that row's values, the token lies
+                # in the temperature-only support (a finite logit) and
+                # inside the sequence's own filters
+                p = s.params
+                row = seen[(i, at - 1)].cpu()
+                assert so.in_support(row, t, T, 0, 1.0) and so.in_support(
+                    row, t, T, p.top_k or 0, p.top_p or 1.0), \
+                    f"{what}: seq {i} first token outside the support"
+            elif tail == "gumbel":
                 # the in-graph Gumbel tail: the counter is bufs["lens"],
                 # the KV length the tail sees = tokens in the sequence
                 # once the fed token is appended = the produced token's
