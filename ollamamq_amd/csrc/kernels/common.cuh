@@ -1,6 +1,7 @@
-// Shared device helpers and the two layout contracts every kernel file
-// here depends on: the activation-fragment ("frag") layout and the paged
-// KV pool addressing.  This header is the ONLY definition of either; the
+// Shared device helpers and the layout contracts every kernel file here
+// depends on: the activation-fragment ("frag") layout, the FP8 weight pack
+// and the paged KV pool addressing.  This header is the ONLY definition of
+// each; the
 // .hip files include it and point here instead of restating the maths.
 #pragma once
 
@@ -68,6 +69,48 @@ DEV int64_t frag_unit(int m, int c) {
 // element offset of (m, kcol)
 DEV int64_t frag_off(int m, int kcol) {
     return frag_unit(m, kcol >> 3) * 8 + (kcol & 7);
+}
+
+// ---------------------------------------------------------------------------
+// FP8 weight pack (OCP e4m3fn codes, one byte per element): the same
+// 32-row tiles and 64-wide k-blocks as the bf16 pack, but a k-block is two
+// 16-byte units per lane instead of four, and each unit carries TWO of the
+// lane's 8-element MFMA fragments: W[t*32 + r][k], k = b*64 + j*16 + h*8 + e,
+// sits in 16-byte unit ((t*NB + b)*2 + (j >> 1))*64 + h*32 + r at byte
+// (j & 1)*8 + e.  One dwordx4 load therefore feeds fragments j = 2*jj and
+// 2*jj + 1 of the lane (ops/hip.py pack_weight_fp8 spells the same order).
+// The per-row dequantisation scales are a separate fp32 vector in PACK row
+// order: scale[t*32 + r] belongs to the row stored as row r of tile t.
+// ---------------------------------------------------------------------------
+// byte offset of W[t*32 + r][k] in a packed fp8 tile stream, NB = K/64
+DEV int64_t fp8_pack_off(int t, int r, int k, int NB) {
+    const int b = k >> 6, j = (k >> 4) & 3, h = (k >> 3) & 1, e = k & 7;
+    return ((((int64_t)t * NB + b) * 2 + (j >> 1)) * 64 + h * 32 + r) * 16
+           + (j & 1) * 8 + e;
+}
+
+// 8 e4m3fn codes (two dwords, ascending k) -> 8 bf16.  v_cvt_pk_f32_fp8
+// widens two codes exactly; every e4m3 value fits bf16's 8 significant
+// bits, so keeping the high half of each fp32 is exact as well (no
+// rounding happens anywhere: subnormal codes are normal fp32 numbers).
+DEV bf16x8 fp8x8_to_bf16x8(unsigned lo, unsigned hi) {
+    typedef __attribute__((ext_vector_type(2))) float f32x2;
+    typedef __attribute__((ext_vector_type(4))) unsigned int u32x4_t;
+    union { u32x4_t u; bf16x8 v; } out;
+    const f32x2 f0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, false);
+    const f32x2 f1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)lo, true);
+    const f32x2 f2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, false);
+    const f32x2 f3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)hi, true);
+    // v_perm_b32 selector 0x07060302: {hi16(first arg), hi16(second arg)}
+    out.u.x = __builtin_amdgcn_perm(__float_as_uint(f0.y),
+                                    __float_as_uint(f0.x), 0x07060302u);
+    out.u.y = __builtin_amdgcn_perm(__float_as_uint(f1.y),
+                                    __float_as_uint(f1.x), 0x07060302u);
+    out.u.z = __builtin_amdgcn_perm(__float_as_uint(f2.y),
+                                    __float_as_uint(f2.x), 0x07060302u);
+    out.u.w = __builtin_amdgcn_perm(__float_as_uint(f3.y),
+                                    __float_as_uint(f3.x), 0x07060302u);
+    return out.v;
 }
 
 // ---------------------------------------------------------------------------

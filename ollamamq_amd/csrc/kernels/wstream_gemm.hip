@@ -29,6 +29,10 @@
 // end-of-kernel LDS reduce (the ONE barrier, after all streaming).
 // ksplit>1 writes fp32 partials; k_wstream_combine folds them (+bias).
 //
+// Weights may also be FP8 (e4m3) codes with per-row power-of-two scales
+// (WF = 1, see k_wstream_gemm): half the stream, widened to bf16 in
+// registers in front of the same MFMA sequence.
+//
 // Activations may arrive and leave in the frag layout (XLDS=2 / yfrag):
 // the same fragment order applied to a [32, K] activation, defined with
 // frag_off in common.cuh.
@@ -41,6 +45,9 @@ union u4bf8 { u32x4 u; bf16x8 v; };
 // Pure-stream diagnostic: same grid/geometry/addressing as the GEMM but
 // only the nt weight loads (no x, no MFMA) — measures this geometry's
 // load-path ceiling so kernel iterations know what they are chasing.
+// WF: weight format, 0 = bf16 pack (4 units per lane and k-block),
+// 1 = fp8 pack (2 units, common.cuh "FP8 weight pack").
+template <int WF>
 __global__ __launch_bounds__(512) void k_wstream_pure(
     float* __restrict__ sink, const u32x4* __restrict__ wp,
     int N, int K, int ksplit)
@@ -55,23 +62,31 @@ __global__ __launch_bounds__(512) void k_wstream_pure(
     const int b_lo = (int)(((int64_t)gw * NB) / GW);
     const int b_hi = (int)(((int64_t)(gw + 1) * NB) / GW);
     unsigned acc = 0;
-    const u32x4* wq = wp + (((int64_t)t * NB + b_lo) * 4) * 64 + lane;
-    for (int b = b_lo; b < b_hi; ++b, wq += 256) {
+    constexpr int UPB = WF ? 2 : 4;        // 16-byte units per lane, block
+    const u32x4* wq = wp + (((int64_t)t * NB + b_lo) * UPB) * 64 + lane;
+    for (int b = b_lo; b < b_hi; ++b, wq += UPB * 64) {
         u32x4 v0 = __builtin_nontemporal_load(wq);
         u32x4 v1 = __builtin_nontemporal_load(wq + 64);
-        u32x4 v2 = __builtin_nontemporal_load(wq + 128);
-        u32x4 v3 = __builtin_nontemporal_load(wq + 192);
-        acc ^= v0.x ^ v0.w ^ v1.x ^ v1.w ^ v2.x ^ v2.w ^ v3.x ^ v3.w;
+        acc ^= v0.x ^ v0.w ^ v1.x ^ v1.w;
+        if (!WF) {
+            u32x4 v2 = __builtin_nontemporal_load(wq + 128);
+            u32x4 v3 = __builtin_nontemporal_load(wq + 192);
+            acc ^= v2.x ^ v2.w ^ v3.x ^ v3.w;
+        }
     }
     if (acc == 0xDEADBEEFu) sink[0] = 1.f;   // never: keeps loads alive
 }
 
 extern "C" int wstream_pure_bf16(void* sink, const void* wp, int N, int K,
-                                 int ksplit, hipStream_t stream)
+                                 int ksplit, int wfmt, hipStream_t stream)
 {
     dim3 grid(N / 32, ksplit);
-    k_wstream_pure<<<grid, 512, 0, stream>>>(
-        (float*)sink, (const u32x4*)wp, N, K, ksplit);
+    if (wfmt)
+        k_wstream_pure<1><<<grid, 512, 0, stream>>>(
+            (float*)sink, (const u32x4*)wp, N, K, ksplit);
+    else
+        k_wstream_pure<0><<<grid, 512, 0, stream>>>(
+            (float*)sink, (const u32x4*)wp, N, K, ksplit);
     return (int)hipGetLastError();
 }
 
@@ -137,7 +152,21 @@ DEV void spill_acc(float (*red8)[32][32], const f32x16& acc, int wid,
     __syncthreads();
 }
 
-template <int MT, int DEPTH = 1, int XLDS = 0, int GU = 0, int RP = 0>
+// WF (weight format): 0 = bf16 pack; 1 = fp8 pack (OCP e4m3fn codes,
+// common.cuh "FP8 weight pack") with a per-row fp32 power-of-two scale
+// vector `wscale` in PACK row order.  The fp8 variant differs only in how
+// B fragments reach registers: a k-block is two 16-byte loads per lane,
+// each widened in registers to two bf16 fragments that feed the SAME
+// bf16 MFMA sequence over the same wave k-ranges in the same ascending
+// order.  The scale multiplies the cross-wave-reduced sum before anything
+// else in the epilogue; a power of two commutes with every fp32 rounding,
+// so the result is bit-equal to the bf16 kernel over the dequantised
+// weights.  A k-block being half the bytes, the fp8 stream keeps TWO
+// k-blocks in flight per wave (the two-slot ring of DEPTH == 2: the same
+// 4 KiB and the same 4 load registers as the bf16 DEPTH == 1 stream);
+// fp8 is instantiated for DEPTH == 1 only.
+template <int MT, int DEPTH = 1, int XLDS = 0, int GU = 0, int RP = 0,
+          int WF = 0>
 __global__ __launch_bounds__(512) void k_wstream_gemm(
     bf16* __restrict__ y,            // [M, N] (ksplit == 1)
     float* __restrict__ part,        // [ksplit, M, N] (ksplit > 1)
@@ -147,8 +176,12 @@ __global__ __launch_bounds__(512) void k_wstream_gemm(
     int M, int N, int K, int64_t xs, int ksplit,
     const float* __restrict__ rstd_parts, int rstd_nt, float inv_h,
     float eps, const bf16* __restrict__ res_in,
-    float* __restrict__ sq_parts, RopeEpi rp = {}, int yfrag = 0)
+    float* __restrict__ sq_parts, RopeEpi rp = {}, int yfrag = 0,
+    const float* __restrict__ wscale = nullptr)   // [N], WF == 1 only
 {
+    static_assert(!WF || DEPTH == 1, "fp8 packs: DEPTH == 1 only");
+    constexpr int UPB = WF ? 2 : 4;        // 16-byte units per lane, block
+    constexpr int RING = (DEPTH == 2 || WF) ? 2 : 1;   // k-blocks in flight
     const int t = blockIdx.x;              // n-tile (32 cols of y)
     const int ks = blockIdx.y;
     const int tid = threadIdx.x;
@@ -181,8 +214,8 @@ __global__ __launch_bounds__(512) void k_wstream_gemm(
 
     f32x16 acc0 = {}, acc1 = {};
     if (b_lo < b_hi) {
-        const u32x4* wbase = wp + ((int64_t)t * NB * 4) * 64 + lane;
-        u4bf8 br[DEPTH][4];
+        const u32x4* wbase = wp + ((int64_t)t * NB * UPB) * 64 + lane;
+        u4bf8 br[RING][UPB];
         bf16x8 a0[2], a1[2], a2[2], a3[2];
         const u4bf8* xf = reinterpret_cast<const u4bf8*>(x);
         auto lda16 = [&](bf16x8* d, int b, int off) {
@@ -208,15 +241,25 @@ __global__ __launch_bounds__(512) void k_wstream_gemm(
         // instead of branching per lane (the tail never computes it)
         auto ldb = [&](int s, int b) {
             const u32x4* q = wbase + (int64_t)(b < b_hi ? b : b_hi - 1)
-                                     * 256;
+                                     * (UPB * 64);
             br[s][0].u = __builtin_nontemporal_load(q);
             br[s][1].u = __builtin_nontemporal_load(q + 64);
-            br[s][2].u = __builtin_nontemporal_load(q + 128);
-            br[s][3].u = __builtin_nontemporal_load(q + 192);
+            if constexpr (!WF) {
+                br[s][2].u = __builtin_nontemporal_load(q + 128);
+                br[s][3].u = __builtin_nontemporal_load(q + 192);
+            }
         };
         auto compute = [&](int s) {
-            bf16x8 vb0 = br[s][0].v, vb1 = br[s][1].v;
-            bf16x8 vb2 = br[s][2].v, vb3 = br[s][3].v;
+            bf16x8 vb0, vb1, vb2, vb3;
+            if constexpr (WF) {      // unit jj holds fragments 2*jj (.xy), 2*jj+1 (.zw)
+                vb0 = fp8x8_to_bf16x8(br[s][0].u.x, br[s][0].u.y);
+                vb1 = fp8x8_to_bf16x8(br[s][0].u.z, br[s][0].u.w);
+                vb2 = fp8x8_to_bf16x8(br[s][1].u.x, br[s][1].u.y);
+                vb3 = fp8x8_to_bf16x8(br[s][1].u.z, br[s][1].u.w);
+            } else {
+                vb0 = br[s][0].v, vb1 = br[s][1].v;
+                vb2 = br[s][2].v, vb3 = br[s][3].v;
+            }
             acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
                 a0[0], vb0, acc0, 0, 0, 0);
             acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
@@ -276,25 +319,51 @@ __global__ __launch_bounds__(512) void k_wstream_gemm(
                 }
             };
             ldb(0, b_lo);
+            if constexpr (RING == 2) ldb(1, b_lo + 1);
             glbx(b_lo);
             dswx(0);
             int b = b_lo;
-            for (; b < b_hi - 1; ++b) {
-                const int s = (b - b_lo) & 1;
-                dsrx(s);
+            if constexpr (RING == 1) {
+                for (; b < b_hi - 1; ++b) {
+                    const int s = (b - b_lo) & 1;
+                    dsrx(s);
+                    compute(0);
+                    ldb(0, b + 1);
+                    glbx(b + 1);
+                    dswx(s ^ 1);
+                }
+                dsrx((b - b_lo) & 1);
                 compute(0);
-                ldb(0, b + 1);
-                glbx(b + 1);
-                dswx(s ^ 1);
+            } else {
+                // two weight slots: block b_lo + i uses weight slot and x
+                // tile i & 1, in the same ascending order as above
+                for (; b + 2 < b_hi; b += 2) {
+                    dsrx(0);
+                    compute(0);
+                    ldb(0, b + 2);
+                    glbx(b + 1);
+                    dswx(1);
+                    dsrx(1);
+                    compute(1);
+                    ldb(1, b + 3);
+                    glbx(b + 2);
+                    dswx(0);
+                }
+                dsrx(0);
+                compute(0);
+                if (b + 1 < b_hi) {
+                    glbx(b + 1);
+                    dswx(1);
+                    dsrx(1);
+                    compute(1);
+                }
             }
-            dsrx((b - b_lo) & 1);
-            compute(0);
         } else {
             ldb(0, b_lo);
-            if (DEPTH == 2) ldb(1, b_lo + 1);
+            if constexpr (RING == 2) ldb(1, b_lo + 1);
             lda(b_lo);
             int b = b_lo;
-            if (DEPTH == 1) {
+            if constexpr (RING == 1) {
                 for (; b < b_hi - 1; ++b) {
                     compute(0);
                     ldb(0, b + 1);
@@ -357,6 +426,10 @@ __global__ __launch_bounds__(512) void k_wstream_gemm(
                     sg += red8[wv][m][c];
                     su += red8[wv][m][c + 16];
                 }
+                if constexpr (WF) {            // pack row order: GU tile
+                    sg *= wscale[t * 32 + c];
+                    su *= wscale[t * 32 + 16 + c];
+                }
                 if (rstd_parts) {              // MT==1 chain only
                     const float rs = rstd_sh[gm];  // pre-silu: nonlinear
                     sg *= rs;
@@ -387,6 +460,10 @@ __global__ __launch_bounds__(512) void k_wstream_gemm(
                     for (int wv = 0; wv < 8; wv++) {
                         lo += red8[wv][m][c];
                         hi += red8[wv][m][c + 16];
+                    }
+                    if constexpr (WF) {   // pair-ordered like the pack
+                        lo *= wscale[t * 32 + c];
+                        hi *= wscale[t * 32 + 16 + c];
                     }
                     if (rstd_parts) {
                         const float rs = rstd_sh[gm];
@@ -429,6 +506,7 @@ __global__ __launch_bounds__(512) void k_wstream_gemm(
                         #pragma unroll
                         for (int wv = 0; wv < 8; wv++)
                             sv += red8[wv][mr][n];
+                        if constexpr (WF) sv *= wscale[t * 32 + n];
                         if (rstd_parts) sv *= rstd_sh[gm];
                         if (bias)
                             sv += __bfloat162float(bias[t * 32 + n]);
@@ -456,6 +534,7 @@ __global__ __launch_bounds__(512) void k_wstream_gemm(
                 #pragma unroll
                 for (int wv = 0; wv < 8; wv++)
                     s += red8[wv][mr][n];
+                if constexpr (WF) s *= wscale[n0 + n];
                 if (ksplit == 1) {
                     if (rstd_parts) s *= rstd_sh[m];
                     if (bias) s += __bfloat162float(bias[n0 + n]);
@@ -511,21 +590,37 @@ struct WsArgs {
     void* sq_parts;
     RopeEpi rp;
     int yfrag;
+    const void* wscale;   // fp8 pack: [N] fp32 row scales; null = bf16 pack
 };
 
 // The one launch site.  Dynamic LDS: the 8-wave reduce space (32 KiB), or
 // the 8 double-buffered 4 KiB x tiles it aliases when XLDS == 1 (64 KiB),
 // plus the 256 B rstd tail.
-template <int MT, int DEPTH, int XLDS, int GU, int RP>
-static void ws_launch(const WsArgs& a, hipStream_t stream)
+template <int MT, int DEPTH, int XLDS, int GU, int RP, int WF>
+static void ws_launch_wf(const WsArgs& a, hipStream_t stream)
 {
     const int lds = (XLDS == 1 ? 16 * 4096 : 8 * 32 * 32 * 4) + 256;
     dim3 grid(a.N / 32, a.ksplit);
-    k_wstream_gemm<MT, DEPTH, XLDS, GU, RP><<<grid, 512, lds, stream>>>(
+    k_wstream_gemm<MT, DEPTH, XLDS, GU, RP, WF><<<grid, 512, lds, stream>>>(
         (bf16*)a.y, (float*)a.part, (const bf16*)a.x, (const u32x4*)a.wp,
         (const bf16*)a.bias, a.M, a.N, a.K, a.xs, a.ksplit,
         (const float*)a.rstd_parts, a.rstd_nt, a.inv_h, a.eps,
-        (const bf16*)a.res_in, (float*)a.sq_parts, a.rp, a.yfrag);
+        (const bf16*)a.res_in, (float*)a.sq_parts, a.rp, a.yfrag,
+        (const float*)a.wscale);
+}
+
+// A scale vector selects the fp8 instantiation of the same geometry.  fp8
+// exists at DEPTH == 1 only: the entry points answer WS_ERR_FP8_DEPTH
+// before they get here, so nothing is launched for that combination.
+constexpr int WS_ERR_FP8_DEPTH = -103;
+
+template <int MT, int DEPTH, int XLDS, int GU, int RP>
+static void ws_launch(const WsArgs& a, hipStream_t stream)
+{
+    if (!a.wscale)
+        ws_launch_wf<MT, DEPTH, XLDS, GU, RP, 0>(a, stream);
+    else if constexpr (DEPTH == 1)
+        ws_launch_wf<MT, 1, XLDS, GU, RP, 1>(a, stream);
 }
 
 // Fused gate_up @ SwiGLU over GU-interleaved packed weights.
@@ -534,11 +629,12 @@ static void ws_launch(const WsArgs& a, hipStream_t stream)
 extern "C" int wstream_gu_bf16(
     void* act, const void* x, const void* wp, int M, int N, int K,
     int64_t xs, int xlds, const void* rstd_parts, int rstd_nt,
-    float inv_h, float eps, int yfrag, hipStream_t stream)
+    float inv_h, float eps, int yfrag, const void* wscale,
+    hipStream_t stream)
 {
     const WsArgs a{act, nullptr, x, wp, nullptr, M, N, K, xs, 1,
                    rstd_parts, rstd_nt, inv_h, eps, nullptr, nullptr, {},
-                   yfrag};
+                   yfrag, wscale};
     if (M > 32) {
         if (xlds == 2)         // frag chain at batches 33..64
             ws_launch<2, 1, 2, 1, 0>(a, stream);
@@ -623,15 +719,17 @@ extern "C" int wstream_gemm_bf16(
     void* y, void* part, const void* x, const void* wp, const void* bias,
     int M, int N, int K, int64_t xs, int ksplit, int depth, int xlds,
     const void* rstd_parts, int rstd_nt, float inv_h, float eps,
-    const void* res_in, void* sq_parts, int yfrag, hipStream_t stream)
+    const void* res_in, void* sq_parts, int yfrag, const void* wscale,
+    hipStream_t stream)
 {
     if (ksplit > 1 && rstd_parts) return -100;     // fused rstd needs ks==1
+    if (wscale && depth != 1) return WS_ERR_FP8_DEPTH;
     // the residual add and the sq partials belong to whoever writes y:
     // this kernel at ksplit == 1, the tile combine below otherwise
     const WsArgs a{y, part, x, wp, bias, M, N, K, xs, ksplit,
                    rstd_parts, rstd_nt, inv_h, eps,
                    ksplit == 1 ? res_in : nullptr,
-                   ksplit == 1 ? sq_parts : nullptr, {}, yfrag};
+                   ksplit == 1 ? sq_parts : nullptr, {}, yfrag, wscale};
     if (M <= 32) {
         if (xlds == 2)
             ws_launch<1, 1, 2, 0, 0>(a, stream);
@@ -678,14 +776,15 @@ extern "C" int wstream_qkv_rope_bf16(
     const void* rstd_parts, int rstd_nt, float inv_h, float eps,
     const void* rcos, const void* rsin, const void* pos,
     const void* slot, const void* ptab, void* kp, void* vp,
-    int nl, int nkl, int psz, int maxp, int xf, hipStream_t stream)
+    int nl, int nkl, int psz, int maxp, int xf, const void* wscale,
+    hipStream_t stream)
 {
     const RopeEpi rp{(const float*)rcos, (const float*)rsin,
                      (const int*)pos, (const int*)slot, (const int*)ptab,
                      (bf16*)kp, (bf16*)vp, nl, nkl, psz, maxp};
     const WsArgs a{y, nullptr, x, wp, bias, M, N, K, xs, 1,
                    rstd_parts, rstd_nt, inv_h, eps, nullptr, nullptr, rp,
-                   0};
+                   0, wscale};
     if (xf && M > 32)
         ws_launch<2, 1, 2, 0, 1>(a, stream);
     else if (xf)

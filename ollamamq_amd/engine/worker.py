@@ -35,6 +35,7 @@ from typing import Dict, Optional
 import torch
 
 from ..models import LlamaModel, PRESETS
+from ..models.llama import model_size_bytes, quantization_level
 from .engine import GenParams, LlamaEngine
 from .kvcache import PagedKVCache
 from .tokenizer import ByteTokenizer
@@ -570,17 +571,14 @@ class Conn:
             # Ollama tags/ps entry schema (name/model/size/digest/details)
             import hashlib
             cfg = PRESETS.get(m)
-            qd = cfg.n_heads * cfg.head_dim if cfg else 0
-            kvd = cfg.n_kv_heads * cfg.head_dim if cfg else 0
-            size = 2 * (cfg.vocab * cfg.hidden * 2 + cfg.n_layers *
-                        (cfg.hidden * (qd + 2 * kvd) + qd * cfg.hidden +
-                         3 * cfg.hidden * cfg.ffn)) if cfg else 0
+            size = model_size_bytes(cfg) if cfg else 0
+            quant = quantization_level(cfg) if cfg else "BF16"
             e = {"name": m, "model": m, "size": size,
                  "digest": hashlib.sha256(m.encode()).hexdigest(),
                  "modified_at": _now_iso(),
                  "details": {"format": "safetensors", "family": "llama",
                              "families": ["llama"], "parameter_size": m,
-                             "quantization_level": "BF16"}}
+                             "quantization_level": quant}}
             if res:
                 e["size_vram"] = size
                 e["expires_at"] = _now_iso()
@@ -630,7 +628,7 @@ class Conn:
                 "details": {"format": "safetensors", "family": "llama",
                             "families": ["llama"],
                             "parameter_size": cfg.name,
-                            "quantization_level": "BF16"},
+                            "quantization_level": quantization_level(cfg)},
                 "model_info": {
                     "general.architecture": "llama",
                     "llama.block_count": cfg.n_layers,

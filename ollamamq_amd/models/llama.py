@@ -16,6 +16,7 @@ Design notes (MI355X):
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 from dataclasses import dataclass, field
 from typing import Optional
@@ -45,6 +46,10 @@ class LlamaConfig:
     # Llama-3.1-style NTK rope scaling (factor, low_freq_factor,
     # high_freq_factor, original_max_ctx); None = plain RoPE
     rope_scaling: Optional[tuple] = None
+    # weight-only quantisation of the projections and the LM head: "" (bf16)
+    # or "fp8" (OCP e4m3fn codes, per-output-row power-of-two scales; the
+    # live weights hold the dequantised values, see _quant_global)
+    quant: str = ""
 
     @property
     def q_dim(self) -> int:
@@ -123,6 +128,48 @@ PRESETS = {
     ),
 }
 
+# FP8 weight-only twins, appended AFTER every bf16 preset so name matching
+# that walks PRESETS in order still meets the bf16 model first.
+for _base in ("llama3-8b", "llama3-70b", "llama3.1-8b", "llama2-7b",
+              "llama2-13b", "qwen2-7b", "mistral-7b", "tiny"):
+    PRESETS[_base + "-fp8"] = dataclasses.replace(
+        PRESETS[_base], name=_base + "-fp8", quant="fp8")
+del _base
+
+
+def quantization_level(cfg) -> str:
+    """Ollama's details.quantization_level of a config."""
+    return "FP8_E4M3" if cfg.quant == "fp8" else "BF16"
+
+
+def model_size_bytes(cfg) -> int:
+    """Reported model size: bf16 everywhere, except that a quantised
+    config counts its quantised matrices (the projections and the LM head)
+    at one byte per element; embed stays bf16."""
+    proj = cfg.n_layers * (cfg.hidden * (cfg.q_dim + 2 * cfg.kv_dim)
+                           + cfg.q_dim * cfg.hidden
+                           + 3 * cfg.hidden * cfg.ffn)
+    table = cfg.vocab * cfg.hidden
+    if cfg.quant == "fp8":
+        return 2 * table + table + proj
+    return 2 * (2 * table + proj)
+
+
+def _quant_global(cfg, w):
+    """Model-build quantisation of a GLOBAL matrix (before any TP slicing,
+    so the row scales come from the global rows and TP=N shards are slices
+    of the TP=1 weights; after the norm fold — the norm weights are ones
+    here, a checkpoint loader folds first).  The matrix is replaced by its
+    dequantised values, exact in bf16: the library prefill path, the CPU
+    reference path and the fp8 streaming packs (built later from these
+    live weights) all compute with the same numbers."""
+    if not cfg.quant:
+        return w
+    if cfg.quant != "fp8":
+        raise ValueError(f"unknown quant {cfg.quant!r} (\"\" or \"fp8\")")
+    from ..ops.quant import dequantize_fp8_weight
+    return dequantize_fp8_weight(w)
+
 
 def _randn(shape, dev, dtype, gen, scale):
     # generate on the generator's own device (CPU gen => bit-identical
@@ -153,7 +200,8 @@ class LlamaLayer:
         Hq, KVH = cfg.n_heads, cfg.n_kv_heads
         # global fused QKV [Hq*d + 2*KVH*d, h]; column-parallel: this rank
         # keeps its q-head rows + its kv-head rows
-        wqkv_g = _randn(((Hq + 2 * KVH) * d, h), dev, dtype, gen, scale)
+        wqkv_g = _quant_global(
+            cfg, _randn(((Hq + 2 * KVH) * d, h), dev, dtype, gen, scale))
         q = wqkv_g[rank * nh * d:(rank + 1) * nh * d]
         k = wqkv_g[Hq * d + rank * nkv * d: Hq * d + (rank + 1) * nkv * d]
         v = wqkv_g[(Hq + KVH) * d + rank * nkv * d:
@@ -171,18 +219,19 @@ class LlamaLayer:
             self.bqkv = torch.cat([bq, bk, bv], dim=0).contiguous()
             del b_g
         # row-parallel output projection: columns of the global [h, Hq*d]
-        wo_g = _randn((h, Hq * d), dev, dtype, gen, scale)
+        wo_g = _quant_global(cfg, _randn((h, Hq * d), dev, dtype, gen, scale))
         self.wo = wo_g[:, rank * nh * d:(rank + 1) * nh * d].contiguous()
         del wo_g
         # column-parallel gate+up: global [2F, h], shard gate + up rows
         F, f = cfg.ffn, cfg.ffn // tp
-        wgu_g = _randn((2 * F, h), dev, dtype, gen, scale)
+        wgu_g = _quant_global(cfg, _randn((2 * F, h), dev, dtype, gen, scale))
         self.wgate_up = torch.cat(
             [wgu_g[rank * f:(rank + 1) * f],
              wgu_g[F + rank * f:F + (rank + 1) * f]], dim=0).contiguous()
         del wgu_g
         # row-parallel down: columns of the global [h, F]
-        wd_g = _randn((h, F), dev, dtype, gen, 1.0 / math.sqrt(cfg.ffn))
+        wd_g = _quant_global(
+            cfg, _randn((h, F), dev, dtype, gen, 1.0 / math.sqrt(cfg.ffn)))
         self.wdown = wd_g[:, rank * f:(rank + 1) * f].contiguous()
         del wd_g
         # rmsnorm weights are FOLDED into the projections at build
@@ -245,7 +294,8 @@ class LlamaModel:
         # Vocab-parallel LM head shard: rows of the global [vocab, hidden]
         # (final_norm folds in like the per-layer norms — see LlamaLayer)
         vshard = cfg.vocab // tp_size
-        lm_g = _randn((cfg.vocab, cfg.hidden), dev, dtype, gen, scale)
+        lm_g = _quant_global(
+            cfg, _randn((cfg.vocab, cfg.hidden), dev, dtype, gen, scale))
         self.lm_head = (lm_g[tp_rank * vshard:(tp_rank + 1) * vshard]
                         * self.final_norm).contiguous()
         del lm_g
@@ -284,8 +334,20 @@ class LlamaModel:
         if self.device.type != "cuda" or self.dtype != torch.bfloat16 \
                 or os.environ.get("OLLAMAMQ_NO_PACK") == "1":
             return
+        fp8 = self.cfg.quant == "fp8"
+        if fp8:
+            # fp8 packs are one byte per packed element (embed is not
+            # packed): about half the bf16 copy.  (70B on one 288 GB GPU
+            # measured 3 GiB short of this gate — docs/KERNELS.md "FP8
+            # weights" — and stays on the library GEMMs.)  The build-time
+            # quantisation leaves freed blocks in the caching allocator;
+            # hand them back so the gate sees them.
+            torch.cuda.empty_cache()
+            need = self.weight_bytes() // 2 - self.embed.numel()
+        else:
+            need = self.weight_bytes()
         free, _ = torch.cuda.mem_get_info(self.device)
-        if self.weight_bytes() > free * 0.45:
+        if need > free * 0.45:
             return
         # The rmsnorm WEIGHT is folded into the qkv / gate_up / lm_head
         # packs (rmsnorm(x)*w @ W^T == rmsnorm_unit(x) @ (W*diag(w))^T),
@@ -293,7 +355,13 @@ class LlamaModel:
         # GEMM epilogues carry rstd scaling + residual + stats.  Folded
         # packs are ONLY read by the fused chain; the generic path keeps
         # explicit rmsnorm + unfolded weights.
-        pk = ops.pack_weight
+        # With cfg.quant == "fp8" the live weights already hold dequantised
+        # values, so requantising them is exact and the fp8 packs stay
+        # pure layout transforms of the live weights, with an encoding.
+        pk = ops.pack_weight_fp8 if fp8 else ops.pack_weight
+        pk_gu = ops.pack_weight_gu_fp8 if fp8 else ops.pack_weight_gu
+        pk_qkv = ops.pack_weight_qkv_rope_fp8 if fp8 \
+            else ops.pack_weight_qkv_rope
         try:
             for l in self.layers:
                 # qkv pack is PAIR-ORDERED for the fused RoPE/KV-append
@@ -301,9 +369,8 @@ class LlamaModel:
                 # Norm weights are already folded at build, so the packs
                 # are pure layout transforms of the live weights.
                 if self.cfg.head_dim == 128:
-                    l.wqkv_pk = ops.pack_weight_qkv_rope(
-                        l.wqkv, self.n_local_heads,
-                        self.n_local_kv_heads)
+                    l.wqkv_pk = pk_qkv(l.wqkv, self.n_local_heads,
+                                       self.n_local_kv_heads)
                     if l.bqkv is not None:
                         l.bqkv_rp = ops.qkv_rope_bias_order(
                             l.bqkv, self.n_local_heads,
@@ -311,7 +378,7 @@ class LlamaModel:
                 else:
                     l.wqkv_pk = None
                 l.wo_pk = pk(l.wo)
-                l.wgu_pk = ops.pack_weight_gu(l.wgate_up)
+                l.wgu_pk = pk_gu(l.wgate_up)
                 l.wdown_pk = pk(l.wdown)
             self.lm_head_pk = pk(self.lm_head)
         except torch.cuda.OutOfMemoryError:

@@ -46,10 +46,10 @@ def _signatures():
                               i, i, i, i, i, f, i64, i, vp],
         "embed_gather_bf16": [vp, vp, vp, i, i, vp],
         "wstream_gemm_bf16": [vp, vp, vp, vp, vp, i, i, i, i64, i,
-                              i, i, vp, i, f, f, vp, vp, i, vp],
-        "wstream_pure_bf16": [vp, vp, i, i, i, vp],
+                              i, i, vp, i, f, f, vp, vp, i, vp, vp],
+        "wstream_pure_bf16": [vp, vp, i, i, i, i, vp],
         "wstream_gu_bf16": [vp, vp, vp, i, i, i, i64, i,
-                            vp, i, f, f, i, vp],
+                            vp, i, f, f, i, vp, vp],
         "row_sumsq_bf16": [vp, vp, i, i, vp],
         "fragify_sumsq_bf16": [vp, vp, vp, i, i, vp],
         "sample_gumbel_bf16": [vp, vp, vp, vp, vp, vp, i, i,
@@ -57,7 +57,7 @@ def _signatures():
         "decode_pure_bf16": [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, vp],
         "wstream_qkv_rope_bf16": [vp, vp, vp, vp, i, i, i, i64,
                                   vp, i, f, f, vp, vp, vp, vp,
-                                  vp, vp, vp, i, i, i, i, i, vp],
+                                  vp, vp, vp, i, i, i, i, i, vp, vp],
     }
 
 
@@ -469,9 +469,10 @@ def linear_gu(x, packed, N, rstd=None, rstd_nt=0, inv_h=0.0, eps=0.0,
     act = torch.empty((M, F) if not yfrag
                       else (((M + 31) // 32) * 32 * F,),
                       dtype=x.dtype, device=x.device)
+    wbuf, wscale = _wfmt(packed)
     _check(_lib.wstream_gu_bf16(
-        _p(act), _p(x), _p(packed), M, N, K, xs, xlds,
-        _p(rstd), rstd_nt, float(inv_h), float(eps), yfrag,
+        _p(act), _p(x), _p(wbuf), M, N, K, xs, xlds,
+        _p(rstd), rstd_nt, float(inv_h), float(eps), yfrag, _p(wscale),
         _stream()), "wstream_gu")
     return act
 
@@ -503,6 +504,105 @@ def pack_weight_qkv_rope(w, nl, nkl):
     return pack_weight(w.index_select(0, order).contiguous())
 
 
+# ---------------------------------------------------------------------------
+# FP8 (OCP e4m3fn) weight-only quantisation: per-output-row power-of-two
+# scales, codes stored in the fp8 pack order of csrc/kernels/common.cuh.
+# The quantiser itself is ops/quant.py; the packs are pure torch and work
+# on CPU tensors too.
+
+from .quant import quantize_fp8, e4m3_decode  # noqa: E402
+
+
+class Fp8Pack:
+    """A packed fp8 weight: `codes` (flat uint8, fp8 pack order), `scale`
+    (fp32 [N] power-of-two row scales in PACK row order) and `order`, the
+    row order the pack was built with: ("plain",), ("gu",) or
+    ("qkv", nl, nkl)."""
+    __slots__ = ("codes", "scale", "order")
+
+    def __init__(self, codes, scale, order):
+        self.codes, self.scale, self.order = codes, scale, order
+
+    def nbytes(self):
+        return self.codes.numel() + self.scale.numel() * 4
+
+
+def _pack_rows(order, N, device):
+    """natural row index of each pack row, or None for the identity."""
+    if order[0] == "gu":
+        F = N // 2
+        idx = torch.arange(N, device=device).reshape(2, F // 16, 16)
+        return idx.permute(1, 0, 2).reshape(-1)
+    if order[0] == "qkv":
+        return torch.tensor(qkv_rope_order(order[1], order[2]), device=device)
+    return None
+
+
+def pack_fp8_codes(codes, e, order=("plain",)):
+    """Lay out natural-order e4m3fn codes [N, K] (uint8) and row exponents
+    [N] (int32) as an Fp8Pack: rows and scales permuted by `order`, then
+    the fp8 pack layout.  The ONE spelling of that layout on the host."""
+    N, K = codes.shape
+    rows = _pack_rows(order, N, codes.device)
+    if rows is not None:
+        codes, e = codes.index_select(0, rows), e.index_select(0, rows)
+    # (t, r, b, jj, jsub, h, e) -> (t, b, jj, h, r, jsub, e): n = t*32 + r,
+    # k = b*64 + (2*jj + jsub)*16 + h*8 + e  (common.cuh fp8_pack_off)
+    p = codes.reshape(N // 32, 32, K // 64, 2, 2, 2, 8) \
+             .permute(0, 2, 3, 5, 1, 4, 6).contiguous()
+    scale = torch.ldexp(torch.ones(N, dtype=torch.float32,
+                                   device=codes.device), e)
+    return Fp8Pack(p.view(-1), scale, order)
+
+
+def _pack_fp8(w, order):
+    N, K = w.shape
+    if N % 32 or K % 64 or not w.is_contiguous():
+        return None
+    codes, e, _ = quantize_fp8(w)
+    return pack_fp8_codes(codes, e, order)
+
+
+def pack_weight_fp8(w):
+    """fp8 counterpart of pack_weight (natural row order)."""
+    return _pack_fp8(w, ("plain",))
+
+
+def pack_weight_gu_fp8(w):
+    """fp8 counterpart of pack_weight_gu: GU-interleaved rows; the scale
+    vector is interleaved the same way."""
+    if (w.shape[0] // 2) % 16:
+        return None
+    return _pack_fp8(w, ("gu",))
+
+
+def pack_weight_qkv_rope_fp8(w, nl, nkl):
+    """fp8 counterpart of pack_weight_qkv_rope: pair-ordered rows; the
+    scale vector is pair-ordered like bqkv_rp."""
+    return _pack_fp8(w, ("qkv", nl, nkl))
+
+
+def unpack_weight_fp8(pack, N, K):
+    """The bf16 dequantised [N, K] matrix of an Fp8Pack in NATURAL row
+    order (inverse of the pack's layout, row order and encoding)."""
+    codes = pack.codes.reshape(N // 32, K // 64, 2, 2, 32, 2, 8) \
+                      .permute(0, 4, 1, 2, 5, 3, 6).reshape(N, K)
+    dq = (e4m3_decode(codes) * pack.scale.unsqueeze(1)).bfloat16()
+    rows = _pack_rows(pack.order, N, dq.device)
+    if rows is None:
+        return dq
+    out = torch.empty_like(dq)
+    out[rows] = dq
+    return out
+
+
+def _wfmt(packed):
+    """(buffer, scale or None) of either kind of pack."""
+    if isinstance(packed, Fp8Pack):
+        return packed.codes, packed.scale
+    return packed, None
+
+
 def linear_qkv_rope(x, packed, N, bias_rp, cache, layer, positions,
                     slots, cos, sin, nl, nkl, rstd, rstd_nt, inv_h, eps,
                     K=None, M_real=32):
@@ -520,12 +620,13 @@ def linear_qkv_rope(x, packed, N, bias_rp, cache, layer, positions,
     y = torch.empty((M, N), dtype=x.dtype, device=x.device)
     kp, vp = _layer_ptrs(cache, layer)
     pos32, slot32 = _i32(positions), _i32(slots)
+    wbuf, wscale = _wfmt(packed)
     _check(_lib.wstream_qkv_rope_bf16(
-        _p(y), _p(x), _p(packed), _p(bias_rp), M, N, K, xs,
+        _p(y), _p(x), _p(wbuf), _p(bias_rp), M, N, K, xs,
         _p(rstd), rstd_nt, float(inv_h), float(eps),
         _p(cos), _p(sin), _p(pos32), _p(slot32), _p(cache.page_table),
         kp, vp, nl, nkl, cache.page_size, cache.page_table.shape[1],
-        xf, _stream()), "wstream_qkv_rope")
+        xf, _p(wscale), _stream()), "wstream_qkv_rope")
     return y
 
 
@@ -587,7 +688,8 @@ def linear_packed(x, packed, bias, N, ks=None, depth=None, xlds=None,
     emits per-tile sum-of-squares partials for the next GEMM.
     Raises ValueError for combinations the kernels do not implement:
     bias with ks > 1 and res/sq_out, sq_out without res at ks == 1, and
-    yfrag with ks > 1 without res/sq_out."""
+    yfrag with ks > 1 without res/sq_out; an Fp8Pack with depth != 1.
+    `packed` is a bf16 pack (flat tensor) or an Fp8Pack."""
     if K is None:
         M, K = x.shape
         xs = x.stride(0)
@@ -618,6 +720,13 @@ def linear_packed(x, packed, bias, N, ks=None, depth=None, xlds=None,
         raise ValueError("linear_packed: sq_out with ks == 1 needs res "
                          "(partials are only accumulated in the residual "
                          "epilogue)")
+    wbuf, wscale = _wfmt(packed)
+    if depth is None:
+        depth = _WS_DEPTH
+    if wscale is not None and depth != 1:
+        raise ValueError("linear_packed: an fp8 pack streams at depth == 1 "
+                         "only (its two-slot ring already keeps two "
+                         "k-blocks in flight); got depth = %d" % depth)
     part = ctypes.c_void_p(0)
     if ks > 1:
         part = _p(_cached(("ws", M, N, ks, str(x.device)),
@@ -629,10 +738,10 @@ def linear_packed(x, packed, bias, N, ks=None, depth=None, xlds=None,
         # wins on the short ramp-bound ones (qkv/o)
         xlds = (_WS_XLDS if M <= 32 and N * K * 2 > (64 << 20) else 0)
     _check(_lib.wstream_gemm_bf16(
-        _p(y), part, _p(x), _p(packed), _p(bias), M, N, K, xs,
-        ks, depth if depth is not None else _WS_DEPTH, xlds,
+        _p(y), part, _p(x), _p(wbuf), _p(bias), M, N, K, xs,
+        ks, depth, xlds,
         _p(rstd), rstd_nt, float(inv_h), float(eps), _p(res), _p(sq_out),
-        yfrag, _stream()), "wstream_gemm")
+        yfrag, _p(wscale), _stream()), "wstream_gemm")
     return y
 
 
@@ -661,9 +770,12 @@ def row_sumsq(x, out=None):
 
 
 def wstream_pure(packed, N, K, ks):
-    """Bandwidth diagnostic: the GEMM's weight stream alone."""
-    sink = torch.zeros(1, dtype=torch.float32, device=packed.device)
-    _check(_lib.wstream_pure_bf16(_p(sink), _p(packed), N, K, ks,
+    """Bandwidth diagnostic: the GEMM's weight stream alone (either kind
+    of pack)."""
+    wbuf, wscale = _wfmt(packed)
+    sink = torch.zeros(1, dtype=torch.float32, device=wbuf.device)
+    _check(_lib.wstream_pure_bf16(_p(sink), _p(wbuf), N, K, ks,
+                                  0 if wscale is None else 1,
                                   _stream()), "wstream_pure")
     return sink
 

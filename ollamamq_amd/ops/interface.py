@@ -126,6 +126,16 @@ def pack_weight(w):
     return None
 
 
+def pack_weight_fp8(w):
+    """FP8 (e4m3, per-row power-of-two scale) pack for the decode GEMM:
+    an ops.hip.Fp8Pack, or None when the shape does not qualify."""
+    if w.is_cuda:
+        from . import hip
+        if hip.available():
+            return hip.pack_weight_fp8(w)
+    return None
+
+
 def swiglu(gate_up):
     if _use_hip(gate_up):
         from . import hip
@@ -153,6 +163,15 @@ def pack_weight_gu(w):
         from . import hip
         if hip.available():
             return hip.pack_weight_gu(w)
+    return None
+
+
+def pack_weight_gu_fp8(w):
+    """FP8 GU-interleaved pack for the fused gate_up+SwiGLU kernel."""
+    if w.is_cuda:
+        from . import hip
+        if hip.available():
+            return hip.pack_weight_gu_fp8(w)
     return None
 
 
@@ -215,6 +234,15 @@ def pack_weight_qkv_rope(w, nl, nkl):
         from . import hip
         if hip.available():
             return hip.pack_weight_qkv_rope(w, nl, nkl)
+    return None
+
+
+def pack_weight_qkv_rope_fp8(w, nl, nkl):
+    """FP8 pair-ordered qkv pack for the fused RoPE/KV-append epilogue."""
+    if w.is_cuda and w.shape[1] % 64 == 0:
+        from . import hip
+        if hip.available():
+            return hip.pack_weight_qkv_rope_fp8(w, nl, nkl)
     return None
 
 
