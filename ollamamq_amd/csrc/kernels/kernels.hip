@@ -900,3 +900,80 @@ extern "C" int fragify_sumsq_bf16(void* xf, void* sq, const void* x,
         (const bf16*)x, (bf16*)xf, (float*)sq, H);
     return (int)hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------
+// Logit penalties (repeat / presence / frequency; llama.cpp order) with the
+// token history kept on the device, so a penalised decode step stays inside
+// the self-advancing hipGraph.  One 256-thread block per row.
+//   L = clamp(lens[b], 0, max_ctx): the KV length AFTER this step's append.
+//   tok[b] >= 0: hist[slot[b]][L-1] = tok[b]  (inactive rows too).
+//   active row (n != 0 and not rp == 1, pp == 0, fp == 0): for every token v
+//   in the window [L - min(n, L), L) with count c_v:
+//       x = (x <= 0) ? x * rp : x / rp;  x -= c_v * fp + pp;  one bf16 round.
+// The window's last token comes from tok[b], never read back from hist, so
+// the append and the window read do not race.  Phase 1 counts with
+// atomicAdd; the __threadfence() before the block barrier is what makes
+// the adds complete at the barrier.  Phase 2 exchanges each
+// window token's counter with 0: the one thread that receives c > 0 owns
+// the token, every other occurrence receives 0.  Integer counts make the
+// result independent of the order of arrival, and counts[] leaves as it
+// came, all zero.  Ids outside [0, V) are skipped, never indexed with.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_logit_penalty(
+    bf16* __restrict__ logits, int* __restrict__ hist,
+    const int* __restrict__ slot, const int* __restrict__ lens,
+    const int* __restrict__ tok, const int* __restrict__ last_n,
+    const float* __restrict__ rp, const float* __restrict__ pp,
+    const float* __restrict__ fp, int* __restrict__ counts,
+    int V, int max_ctx, int max_slots)
+{
+    const int b = blockIdx.x;
+    const int sl = slot[b];
+    if (sl < 0 || sl >= max_slots) return;
+    const int L = min(max(lens[b], 0), max_ctx);
+    const int t_in = tok[b];
+    int* hrow = hist + (int64_t)sl * max_ctx;
+    if (threadIdx.x == 0 && t_in >= 0 && L >= 1) hrow[L - 1] = t_in;
+    const int n = last_n[b];
+    const float r = rp[b], p = pp[b], f = fp[b];
+    if (n == 0 || (r == 1.f && p == 0.f && f == 0.f)) return;
+    const int w = (n < 0 || n > L) ? L : n;
+    const int lo = L - w;
+    bf16* lrow = logits + (int64_t)b * V;
+    int* crow = counts + (int64_t)b * V;
+    // both loops walk the same window positions per thread
+    for (int i = lo + threadIdx.x; i < L; i += 256) {
+        const int t = (i == L - 1 && t_in >= 0) ? t_in : hrow[i];
+        if (t >= 0 && t < V) (void)atomicAdd(&crow[t], 1);
+    }
+    __threadfence();
+    __syncthreads();
+    for (int i = lo + threadIdx.x; i < L; i += 256) {
+        const int t = (i == L - 1 && t_in >= 0) ? t_in : hrow[i];
+        if (t < 0 || t >= V) continue;
+        const int c = atomicExch(&crow[t], 0);
+        if (c > 0) {
+            float x = bf2f(lrow[t]);
+            // each step rounded on its own (no fma contraction), so the
+            // fp32 host reference computes the same bits
+            x = (x <= 0.f) ? __fmul_rn(x, r) : __fdiv_rn(x, r);
+            x = __fsub_rn(x, __fadd_rn(__fmul_rn((float)c, f), p));
+            lrow[t] = f2bf(x);
+        }
+    }
+}
+
+extern "C" int logit_penalty_bf16(
+    void* logits, void* hist, const void* slot, const void* lens,
+    const void* tok, const void* last_n, const void* rp, const void* pp,
+    const void* fp, void* counts, int B, int V, int max_ctx, int max_slots,
+    hipStream_t stream)
+{
+    if (B == 0) return 0;
+    k_logit_penalty<<<B, 256, 0, stream>>>(
+        (bf16*)logits, (int*)hist, (const int*)slot, (const int*)lens,
+        (const int*)tok, (const int*)last_n, (const float*)rp,
+        (const float*)pp, (const float*)fp, (int*)counts, V, max_ctx,
+        max_slots);
+    return (int)hipGetLastError();
+}

@@ -16,6 +16,7 @@ batches whatever it is given).
 from __future__ import annotations
 
 import itertools
+import struct
 import time
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional
@@ -53,6 +54,18 @@ def host_seed_key(seed: int, index: int) -> int:
     return k & 0x7FFFFFFFFFFFFFFF
 
 
+def f32(x) -> float:
+    """x rounded to fp32, the precision the penalty kernel computes in
+    (inf past the fp32 range): host and kernel then judge the same value."""
+    try:
+        return struct.unpack("f", struct.pack("f", float(x)))[0]
+    except OverflowError:
+        return float("inf") if x > 0 else float("-inf")
+
+
+_I32_MAX = (1 << 31) - 1
+
+
 @dataclass
 class GenParams:
     max_tokens: int = 128
@@ -61,6 +74,36 @@ class GenParams:
     top_p: float = 1.0
     stop_token: Optional[int] = None
     seed: Optional[int] = None
+    # logit penalties (llama.cpp / Ollama order, docs/KERNELS.md "Logit
+    # penalties"): over the last repeat_last_n tokens of the sequence,
+    # prompt included (0 = off, -1 = whole sequence).  The defaults
+    # penalise nothing.
+    repeat_penalty: float = 1.0
+    repeat_last_n: int = 64
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+
+    @property
+    def penalty_active(self) -> bool:
+        """The kernel's own predicate, on the fp32 values it sees: a row
+        is inactive when n == 0 or rp == 1, pp == 0, fp == 0."""
+        if self.repeat_last_n == 0 or (
+                self.repeat_penalty == 1.0 and self.presence_penalty == 0.0
+                and self.frequency_penalty == 0.0):
+            return False        # the defaults: no rounding on the hot path
+        return not (
+            f32(self.repeat_penalty) == 1.0
+            and f32(self.presence_penalty) == 0.0
+            and f32(self.frequency_penalty) == 0.0)
+
+    @property
+    def penalty_n(self) -> int:
+        """repeat_last_n as the int32 the kernel takes: 0 for a row
+        without an active penalty; any n past the sequence means the whole
+        sequence, so a larger one is cut to the int32 range."""
+        if not self.penalty_active:
+            return 0
+        return max(-1, min(int(self.repeat_last_n), _I32_MAX))
 
 
 @dataclass
@@ -116,7 +159,15 @@ class LlamaEngine:
         import os as _os
         self.use_graphs = (self.dev.type == "cuda"
                            and _os.environ.get("OLLAMAMQ_NO_GRAPH") != "1")
-        self._graphs: Dict[tuple, dict] = {}   # (batch bucket, class)
+        # (batch bucket, class) for unpenalised batches, (bucket, class, 1)
+        # for batches with a logit penalty (the penalty kernel in-graph)
+        self._graphs: Dict[tuple, dict] = {}
+        # device-resident token history [max_slots, max_ctx] and the
+        # penalty kernel's count scratch [largest bucket, V]: allocated on
+        # the first submit with an active penalty (_ensure_pen), never
+        # inside a capture
+        self._hist = None
+        self._counts = None
         # Pipelined decode: the graph samples (greedy argmax) and advances
         # tok/pos/lens on-device, so steady-state steps skip the H2D input
         # fill AND the host token sync — the host consumes tokens one step
@@ -166,9 +217,19 @@ class LlamaEngine:
         else:
             seq.noise_seed = ((0x5EED0000 ^ (sid * 0x9E3779B1))
                               & 0x7FFFFFFFFFFFFFFF)
+        if params.penalty_active:
+            self._ensure_pen()
         self.seqs[sid] = seq
         self.waiting.append(seq)
         return sid
+
+    def _ensure_pen(self):
+        if self._hist is None:
+            self._hist = torch.zeros((self.kv.max_slots, self.kv.max_ctx),
+                                     dtype=torch.int32, device=self.dev)
+            self._counts = torch.zeros(
+                (self._buckets[-1], self.model.cfg.vocab),
+                dtype=torch.int32, device=self.dev)
 
     def cancel(self, seq_id: int) -> None:
         seq = self.seqs.get(seq_id)
@@ -279,6 +340,14 @@ class LlamaEngine:
                     seq.slot = self.kv.alloc_slot()
                 except RuntimeError:
                     break
+                if seq.params.penalty_active:
+                    # the whole prompt enters the device history once;
+                    # generated tokens reach it only through the penalty
+                    # op's append.  Stream-ordered after any decode step
+                    # still in flight, which touches other slots' rows.
+                    self._hist[seq.slot, :len(seq.prompt)].copy_(
+                        torch.tensor(seq.prompt, dtype=torch.int32)
+                        .to(self.dev, non_blocking=True))
             seq.state = "prefill"
             seq._chunk = take  # tokens of prompt this step
             batch.append(seq)
@@ -309,7 +378,10 @@ class LlamaEngine:
                     if s.prefill_done + s._chunk == len(s.prompt)]
         done_prefill = [batch[i - len(dec)] for i in fin_rows]
         sample_rows = list(range(len(dec))) + fin_rows
-        toks = self._sample(dec + done_prefill, logits[sample_rows])
+        toks = self._sample(dec + done_prefill, logits[sample_rows],
+                            **self._pen_kw(dec + done_prefill,
+                                           token_list[:len(dec)]
+                                           + [-1] * len(done_prefill)))
         now = time.monotonic()
         for s, tok in zip(dec, toks[:len(dec)]):
             s.generated.append(int(tok))
@@ -369,7 +441,45 @@ class LlamaEngine:
                                     meta)
         return logits
 
-    def _sample(self, seqs, logits):
+    def _penalize(self, seqs, logits, pen_tok):
+        """Eager-path logit penalty on the rows about to be sampled:
+        pen_tok[i] is row i's input token this step (appended to the
+        history at its own position) or -1 for a row finishing its
+        prefill, whose prompt is in the history already."""
+        dev = logits.device
+        ints = torch.tensor(
+            [[s.slot for s in seqs],
+             [self.kv.seq_lens[s.slot] for s in seqs],
+             list(pen_tok),
+             [s.params.penalty_n for s in seqs]],
+            dtype=torch.int32).to(dev)
+        flts = torch.tensor(
+            [[s.params.repeat_penalty for s in seqs],
+             [s.params.presence_penalty for s in seqs],
+             [s.params.frequency_penalty for s in seqs]],
+            dtype=torch.float32).to(dev)
+        return ops.penalize_logits(
+            logits, self._hist, ints[0], ints[1], ints[2], ints[3],
+            flts[0], flts[1], flts[2], self._counts)
+
+    @staticmethod
+    def _pen_kw(seqs, pen_tok, penalized=False):
+        """_sample's penalty arguments; none for an unpenalised batch,
+        whose call stays _sample(seqs, logits)."""
+        if not any(s.params.penalty_active for s in seqs):
+            return {}
+        return {"pen_tok": pen_tok, "penalized": penalized}
+
+    def _sample(self, seqs, logits, pen_tok=None, penalized=False):
+        """Sample one token per row.  Rows of a batch with an active logit
+        penalty are penalised here first (pen_tok: see _penalize) unless
+        `penalized` says the logits already are — a penalised graph
+        entry's logits come out of the in-graph kernel, and a second
+        application would penalise twice."""
+        if not penalized and any(s.params.penalty_active for s in seqs):
+            if not logits.is_contiguous():
+                logits = logits.contiguous()
+            logits = self._penalize(seqs, logits, pen_tok)
         dev = logits.device
         temps = torch.tensor([s.params.temperature for s in seqs],
                              dtype=torch.float32, device=dev)
@@ -416,7 +526,9 @@ class LlamaEngine:
         toks: List[int] = []
         if done_prefill:
             sub = logits if len(rows) == len(batch) else logits[rows]
-            toks = self._sample(done_prefill, sub)
+            toks = self._sample(done_prefill, sub,
+                                **self._pen_kw(done_prefill,
+                                               [-1] * len(done_prefill)))
         for s in batch:
             s.prefill_done += s._chunk
             if s.prefill_done == len(s.prompt):
@@ -477,11 +589,12 @@ class LlamaEngine:
             self.kv.ensure(self._dummy_slot, 1)
         return self._dummy_slot
 
-    def _graph_entry(self, B: int, klass: int = 0):
-        """Capture (once per (batch size, sampling class)) a full decode
-        forward as a hipGraph reading its inputs from static device
-        buffers."""
-        entry = self._graphs.get((B, klass))
+    def _graph_entry(self, B: int, klass: int = 0, pen: bool = False):
+        """Capture (once per (batch size, sampling class, penalty flag))
+        a full decode forward as a hipGraph reading its inputs from static
+        device buffers.  Unpenalised entries keep the two-tuple key."""
+        key = (B, klass, 1) if pen else (B, klass)
+        entry = self._graphs.get(key)
         if entry is not None:
             return entry
         dev = self.dev
@@ -498,6 +611,12 @@ class LlamaEngine:
             # advance applies it so pad rows never grow their dummy slot
             "adv": torch.ones(B, dtype=torch.int32, device=dev),
         }
+        if pen:
+            # per-row penalty parameters; last_n = 0 switches a row off
+            bufs["last_n"] = torch.zeros(B, dtype=torch.int32, device=dev)
+            bufs["rp"] = torch.ones(B, dtype=torch.float32, device=dev)
+            bufs["pp"] = torch.zeros(B, dtype=torch.float32, device=dev)
+            bufs["fp"] = torch.zeros(B, dtype=torch.float32, device=dev)
         meta = AttnMeta(
             mode="decode", slot_ids=bufs["slot"], seq_lens=bufs["lens"],
             cu_q=torch.arange(B + 1, dtype=torch.int32, device=dev),
@@ -505,11 +624,11 @@ class LlamaEngine:
             max_q=1, max_kv=self.kv.max_ctx,
             window=getattr(self.model.cfg, "sliding_window", 0))
         entry = {"bufs": bufs, "meta": meta, "graph": None, "logits": None,
-                 "out": None, "ring_i": 0, "klass": klass,
+                 "out": None, "ring_i": 0, "klass": klass, "pen": pen,
                  "pinned": [torch.empty(B, dtype=torch.int64,
                                         pin_memory=True) for _ in range(2)],
                  "events": [torch.cuda.Event() for _ in range(2)]}
-        self._graphs[(B, klass)] = entry
+        self._graphs[key] = entry
         return entry
 
     def _fill_bufs(self, entry, seqs, token_list, pos_list):
@@ -529,6 +648,21 @@ class LlamaEngine:
         bufs["slot"].copy_(staged[2])
         bufs["lens"].copy_(staged[3])
         bufs["adv"].copy_(staged[4])
+        if entry["pen"]:
+            # rows without an active penalty, pad rows among them, carry
+            # last_n = 0: the kernel appends their token and leaves their
+            # logits alone
+            bufs["last_n"].copy_(torch.tensor(
+                [s.params.penalty_n for s in seqs] + [0] * pad,
+                dtype=torch.int32).to(self.dev, non_blocking=True))
+            pen = torch.tensor(
+                [[s.params.repeat_penalty for s in seqs] + [1.0] * pad,
+                 [s.params.presence_penalty for s in seqs] + [0.0] * pad,
+                 [s.params.frequency_penalty for s in seqs] + [0.0] * pad],
+                dtype=torch.float32).to(self.dev, non_blocking=True)
+            bufs["rp"].copy_(pen[0])
+            bufs["pp"].copy_(pen[1])
+            bufs["fp"].copy_(pen[2])
         if entry["klass"] >= 1:
             bufs["temps"].copy_(torch.tensor(
                 [s.params.temperature for s in seqs] + [0.0] * pad,
@@ -599,6 +733,20 @@ class LlamaEngine:
             return torch.where(greedy, am, tok)
         return ops.sample(logits, 0.0, 0, 1.0, None).int()
 
+    def _graph_penalty(self, entry, logits):
+        """The in-graph logit penalty of a penalised entry: right after
+        the forward, before the sampling tail.  bufs["lens"] is the KV
+        length after this step's append and bufs["tok"] the input token,
+        both advanced on-device by the tail, so the history follows the
+        sequence with no host round trip.  A no-op for other entries."""
+        if not entry["pen"]:
+            return logits
+        bufs = entry["bufs"]
+        return ops.penalize_logits(
+            logits, self._hist, bufs["slot"], bufs["lens"], bufs["tok"],
+            bufs["last_n"], bufs["rp"], bufs["pp"], bufs["fp"],
+            self._counts)
+
     def _graph_replay(self, entry):
         bufs, meta = entry["bufs"], entry["meta"]
         if entry["graph"] is None:
@@ -616,6 +764,7 @@ class LlamaEngine:
                     warm_logits = self.model.forward(
                         bufs["tok"], bufs["pos"], self.kv, bufs["slot"],
                         meta)
+                    warm_logits = self._graph_penalty(entry, warm_logits)
                     # eager tail warmup — see _graph_tail docstring
                     self._graph_tail(entry, warm_logits)
             torch.cuda.current_stream().wait_stream(s)
@@ -627,6 +776,8 @@ class LlamaEngine:
                     entry["logits"] = self.model.forward(
                         bufs["tok"], bufs["pos"], self.kv, bufs["slot"],
                         meta)
+                    entry["logits"] = self._graph_penalty(
+                        entry, entry["logits"])
                     # self-advancing tail: sample in-graph and stage the
                     # NEXT step's inputs on-device, so a steady decode
                     # batch replays back-to-back with no host round-trip
@@ -642,20 +793,28 @@ class LlamaEngine:
         entry["graph"].replay()
         return entry["logits"]
 
-    def _decode_forward_graphed(self, seqs, token_list, pos_list):
-        entry = self._graph_entry(self._bucket(len(seqs)))  # class-0:
-        self._fill_bufs(entry, seqs, token_list, pos_list)  # host samples
+    def _decode_forward_graphed(self, seqs, token_list, pos_list,
+                                pen=False):
+        entry = self._graph_entry(self._bucket(len(seqs)),  # class-0:
+                                  0, pen)                   # host samples
+        self._fill_bufs(entry, seqs, token_list, pos_list)
         return self._graph_replay(entry)[:len(seqs)]
 
-    def warm_graphs(self, sizes=None, classes=None):
+    def warm_graphs(self, sizes=None, classes=None, penalty=False):
         """Pre-capture the decode graphs for EVERY (bucket, sampling
         class) at load time — a capture costs ~150 ms and ~75 MB, and a
         LAZY capture mid-serving stalls every in-flight stream for that
         long (a 50%-sampled stress wave against lazy class-1/2 capture
         timed out 189 of 303 requests before this).  With bucketing the
-        set is small and fixed; load time pays ~5-10 s once."""
+        set is small and fixed; load time pays ~5-10 s once.
+
+        penalty=True also captures the penalised twin of every graph
+        (and allocates the history and count buffers); otherwise those
+        are captured lazily by the first penalised batch of each shape."""
         if not self.use_graphs:
             return
+        if penalty:
+            self._ensure_pen()
         if classes is None:
             classes = (0, 1, 2) if self._GRAPH_TOPK else (0, 1)
         sizes = [b for b in (sizes or self._buckets)
@@ -674,8 +833,10 @@ class LlamaEngine:
             host = torch.tensor(
                 [[0] * b, [0] * b, slots, [1] * b], dtype=torch.int32)
             staged = host.to(self.dev, non_blocking=True)
-            for kl in classes:
-                entry = self._graph_entry(b, kl)
+            for kl, pen in ((kl, pen) for kl in classes
+                            for pen in ((False, True) if penalty
+                                        else (False,))):
+                entry = self._graph_entry(b, kl, pen)
                 for i, k in enumerate(("tok", "pos", "slot", "lens")):
                     entry["bufs"][k].copy_(staged[i])
                 self._graph_replay(entry)
@@ -700,14 +861,19 @@ class LlamaEngine:
         token_list = [s.generated[-1] for s in seqs]
         pos_list = [s.total_len - 1 for s in seqs]
         q_lens = [1] * len(seqs)
+        pen = any(s.params.penalty_active for s in seqs)
         if self.use_graphs:
             for s in seqs:
                 self.kv.ensure(s.slot, self.kv.seq_lens[s.slot] + 1)
-            logits = self._decode_forward_graphed(seqs, token_list, pos_list)
+            logits = self._decode_forward_graphed(seqs, token_list,
+                                                  pos_list, pen)
         else:
             logits = self._forward(seqs, token_list, pos_list, q_lens,
                                    "decode")
-        toks = self._sample(seqs, logits)
+        # a penalised graph entry's logits are penalised already
+        toks = self._sample(seqs, logits,
+                            **self._pen_kw(seqs, token_list,
+                                           pen and self.use_graphs))
         now = time.monotonic()
         for s, tok in zip(seqs, toks):
             s.generated.append(int(tok))
@@ -726,13 +892,14 @@ class LlamaEngine:
         tokens stream back asynchronously (pinned ring + event) and the
         PREVIOUS step's tokens are applied while this step runs.
         """
-        key = (tuple(s.seq_id for s in seqs), self._samp_class(seqs))
+        key = (tuple(s.seq_id for s in seqs), self._samp_class(seqs),
+               any(s.params.penalty_active for s in seqs))
         if self._pipe is not None and self._pipe["key"] != key:
             self._drain_pipe()
         # host/device page bookkeeping for the token this replay appends
         for s in seqs:
             self.kv.ensure(s.slot, self.kv.seq_lens[s.slot] + 1)
-        entry = self._graph_entry(self._bucket(len(seqs)), key[1])
+        entry = self._graph_entry(self._bucket(len(seqs)), key[1], key[2])
         if self._pipe is None:
             # (re)sync device input buffers from host truth
             self._fill_bufs(entry, seqs,

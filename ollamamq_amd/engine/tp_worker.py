@@ -91,7 +91,9 @@ class TPWorker(worker_mod.Worker):
             eng = LlamaEngine(m, kv, max_batch=self.max_batch)
             # lockstep capture: every rank reaches warm_graphs at the same
             # op, so the in-graph RCCL collectives pair up across ranks
-            eng.warm_graphs()
+            # (the penalised twins too when asked for, as in worker.py)
+            eng.warm_graphs(penalty=os.environ.get(
+                "OLLAMAMQ_WARM_PENALTY") == "1")
             self.engines[model] = eng
             self.tokenizers[model] = ByteTokenizer(cfg.vocab)
             self.loaded_ctx[model] = ctx

@@ -25,6 +25,7 @@ from __future__ import annotations
 import argparse
 import datetime
 import json
+import math
 import os
 import queue
 import socket
@@ -36,7 +37,7 @@ import torch
 
 from ..models import LlamaModel, PRESETS
 from ..models.llama import model_size_bytes, quantization_level
-from .engine import GenParams, LlamaEngine
+from .engine import GenParams, LlamaEngine, f32
 from .kvcache import PagedKVCache
 from .tokenizer import ByteTokenizer
 
@@ -97,7 +98,11 @@ class Worker:
                     cfg, n_pages=pages, max_slots=self.max_batch + 2,
                     max_ctx=ctx, device=self.device, dtype=self.dtype)
                 eng = LlamaEngine(m, kv, max_batch=self.max_batch)
-                eng.warm_graphs()   # pre-capture: no first-request jitter
+                # pre-capture: no first-request jitter.  The penalised
+                # twins double the graph set, so they are opt-in and
+                # otherwise captured by the first penalised batch.
+                eng.warm_graphs(penalty=os.environ.get(
+                    "OLLAMAMQ_WARM_PENALTY") == "1")
                 self.engines[model] = eng
                 self.tokenizers[model] = ByteTokenizer(cfg.vocab)
                 self.loaded_ctx[model] = ctx
@@ -195,9 +200,49 @@ class Worker:
 
 
 # ------------------------------------------------------------------ wire
+def _number(name: str, v) -> float:
+    """A JSON number or a numeric string, as a float; ValueError otherwise,
+    which the request path answers with a 400."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, str)):
+        raise ValueError(f"{name} must be a number, got {v!r}")
+    try:
+        return float(v)
+    except OverflowError:            # an int past the double range
+        return math.inf if v > 0 else -math.inf
+
+
+def _finite(name: str, v, positive: bool = False) -> float:
+    """A penalty parameter, rounded to the fp32 the kernel computes in and
+    judged there: 1e-60 is 0 and 1e300 is inf in fp32, and either would
+    turn logits into inf or NaN."""
+    x = f32(_number(name, v))
+    if not math.isfinite(x) or (positive and x <= 0):
+        raise ValueError(f"{name} must be finite"
+                         + (" and > 0" if positive else "")
+                         + f" in fp32, got {v!r}")
+    return x
+
+
+def _last_n(v) -> int:
+    """repeat_last_n: an integer >= -1 (0 = off, -1 = whole sequence).  A
+    window longer than any sequence is the whole sequence, so values past
+    the int32 range are cut to it."""
+    x = _number("repeat_last_n", v)
+    if not math.isfinite(x) or x != math.floor(x) or x < -1:
+        raise ValueError(f"repeat_last_n must be an integer >= -1, "
+                         f"got {v!r}")
+    return int(min(x, 2 ** 31 - 1))
+
+
 def _params_from_body(body: dict, tok: ByteTokenizer,
                       openai: bool) -> GenParams:
     opts = body.get("options") or {}
+
+    def pick(key, default):
+        # body first, then options, as temperature: the OpenAI form is
+        # top-level, the Ollama form lives under options
+        v = body.get(key, opts.get(key, default))
+        return default if v is None else v
     max_t = body.get("max_tokens")
     if max_t is None:
         max_t = body.get("max_completion_tokens")
@@ -219,6 +264,15 @@ def _params_from_body(body: dict, tok: ByteTokenizer,
         # not deep inside engine.submit
         seed=(int(seed) if (seed := opts.get("seed", body.get("seed")))
               is not None else None),
+        # logit penalties: a request that names none is not penalised
+        # (Ollama's own default repeat_penalty is 1.1; docs/OPERATIONS.md)
+        repeat_penalty=_finite("repeat_penalty",
+                               pick("repeat_penalty", 1.0), positive=True),
+        repeat_last_n=_last_n(pick("repeat_last_n", 64)),
+        presence_penalty=_finite("presence_penalty",
+                                 pick("presence_penalty", 0.0)),
+        frequency_penalty=_finite("frequency_penalty",
+                                  pick("frequency_penalty", 0.0)),
     )
 
 

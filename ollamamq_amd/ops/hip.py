@@ -58,6 +58,8 @@ def _signatures():
         "wstream_qkv_rope_bf16": [vp, vp, vp, vp, i, i, i, i64,
                                   vp, i, f, f, vp, vp, vp, vp,
                                   vp, vp, vp, i, i, i, i, i, vp, vp],
+        "logit_penalty_bf16": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                               i, i, i, i, vp],
     }
 
 
@@ -817,6 +819,48 @@ def sample_gumbel(logits, temps, seeds, ctrs, noise=None, out=None):
         _p(out), _p(l), _p(temps), _p(seeds), _p(ctrs), _p(noise),
         B, V, pb, pi, sp, _stream()), "sample_gumbel")
     return out
+
+
+def penalize_logits(logits, hist, slot, lens, tok, last_n, rp, pp, fp,
+                    counts):
+    """Repeat / presence / frequency penalties over a device-resident
+    token history, in place (semantics: ops/reference.py penalize_logits;
+    kernel: kernels.hip k_logit_penalty).  Also appends tok[b] >= 0 to
+    hist[slot[b], lens[b] - 1].  `counts` is int32 scratch of at least
+    [B, V], all zero on entry and all zero on exit.  Nothing is allocated
+    here, so the op is safe to call first inside a graph capture."""
+    if logits.dim() != 2 or logits.dtype != torch.bfloat16 \
+            or not logits.is_contiguous():
+        raise ValueError("penalize_logits: logits must be a contiguous "
+                         "[B, V] bf16 tensor")
+    B, V = logits.shape
+    if hist.dim() != 2 or hist.dtype != torch.int32 \
+            or not hist.is_contiguous():
+        raise ValueError("penalize_logits: hist must be a contiguous "
+                         "[max_slots, max_ctx] int32 tensor")
+    if counts.dim() != 2 or counts.dtype != torch.int32 \
+            or not counts.is_contiguous() or counts.shape[1] != V \
+            or counts.shape[0] < B:
+        raise ValueError(f"penalize_logits: counts must be contiguous "
+                         f"int32 [>= {B}, {V}], got {tuple(counts.shape)} "
+                         f"{counts.dtype}")
+    for name, t, dt in (("slot", slot, torch.int32),
+                        ("lens", lens, torch.int32),
+                        ("tok", tok, torch.int32),
+                        ("last_n", last_n, torch.int32),
+                        ("rp", rp, torch.float32),
+                        ("pp", pp, torch.float32),
+                        ("fp", fp, torch.float32)):
+        if t.dtype != dt or t.dim() != 1 or t.shape[0] < B \
+                or not t.is_contiguous() or t.device != logits.device:
+            raise ValueError(f"penalize_logits: {name} must be a contiguous "
+                             f"{dt} vector of at least {B} rows on the "
+                             "logits' device")
+    _check(_lib.logit_penalty_bf16(
+        _p(logits), _p(hist), _p(slot), _p(lens), _p(tok), _p(last_n),
+        _p(rp), _p(pp), _p(fp), _p(counts), B, V, hist.shape[1],
+        hist.shape[0], _stream()), "logit_penalty")
+    return logits
 
 
 def sample(logits, temperature, top_k, top_p, generator=None):

@@ -264,6 +264,19 @@ def qkv_rope_fused(x, packed, N, bias_rp, cache, layer, positions, slots,
                                M_real=M_real)
 
 
+def penalize_logits(logits, hist, slot, lens, tok, last_n, rp, pp, fp,
+                    counts):
+    """Repeat / presence / frequency penalties in place, with the append of
+    this step's input token to the device-resident history (semantics in
+    ops/reference.py).  The caller owns hist and counts."""
+    if _use_hip(logits):
+        from . import hip
+        return hip.penalize_logits(logits, hist, slot, lens, tok, last_n,
+                                   rp, pp, fp, counts)
+    return ref.penalize_logits(logits, hist, slot, lens, tok, last_n,
+                               rp, pp, fp, counts)
+
+
 def sample(logits, temperature, top_k, top_p, generator=None):
     # Sampler: torch ops compose on-GPU; custom fused kernel in ops/hip.py
     # handles the greedy + temperature paths.

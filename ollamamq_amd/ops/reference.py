@@ -164,3 +164,44 @@ def sample(logits, temperature, top_k, top_p, generator=None):
             out[rest] = torch.multinomial(
                 probs, 1, generator=generator).squeeze(1)
     return out
+
+
+def penalize_logits(logits, hist, slot, lens, tok, last_n, rp, pp, fp,
+                    counts=None):
+    """Repeat / presence / frequency penalties (llama.cpp order), in place.
+
+    logits [B, V]; hist [max_slots, max_ctx] int32 token history; slot,
+    lens, tok, last_n [B] int32; rp, pp, fp [B] fp32.  Row b: L = lens[b]
+    clamped to [0, max_ctx] is the KV length AFTER this step's append; a
+    tok[b] >= 0 is first written to hist[slot[b], L-1] (inactive rows
+    too).  A row is active unless last_n == 0 or (rp == 1, pp == 0,
+    fp == 0); its window is the last min(n, L) tokens (n < 0: all L).  For
+    every token v in [0, V) occurring c times in the window, on the fp32
+    value x of the logit: x = x * rp if x <= 0 else x / rp; then
+    x -= c * fp + pp; one rounding back to the logits' dtype.  Every other
+    logit keeps its bits.  `counts` is the HIP kernel's scratch, unused.
+    """
+    B, V = logits.shape
+    max_ctx = hist.shape[1]
+    slots, lens_l = slot.tolist(), lens.tolist()
+    toks, ns = tok.tolist(), last_n.tolist()
+    rp, pp, fp = rp.float(), pp.float(), fp.float()
+    for b in range(B):
+        sl, t_in, n = slots[b], toks[b], ns[b]
+        L = min(max(lens_l[b], 0), max_ctx)
+        if t_in >= 0 and L >= 1:
+            hist[sl, L - 1] = t_in
+        r, p, f = rp[b], pp[b], fp[b]
+        if n == 0 or bool((r == 1) & (p == 0) & (f == 0)):
+            continue
+        w = L if (n < 0 or n > L) else n
+        win = hist[sl, L - w:L].long()
+        win = win[(win >= 0) & (win < V)]
+        if win.numel() == 0:
+            continue
+        ids, c = torch.unique(win, return_counts=True)
+        x = logits[b, ids].float()
+        x = torch.where(x <= 0, x * r, x / r)
+        x = x - (c.float() * f + p)
+        logits[b, ids] = x.to(logits.dtype)
+    return logits

@@ -1,5 +1,5 @@
 """Decode-shape microbench for the small per-step kernels (rmsnorm,
-swiglu, rope_append, argmax): isolates each op at batch B with cold
+swiglu, rope_append, argmax, logit penalty): isolates each op at batch B with cold
 activations (cycled buffers) to see how far each sits above its
 latency floor.  Run on a GPU box: python tools/perf_elementwise.py [B]
 """
@@ -62,6 +62,23 @@ def main():
     cos, sin = ang.cos().to(dev), ang.sin().to(dev)
     bench("rope_append (fused)", lambda i: hip.rope_append(
         cache, 0, qs[i % R], ks[i % R], vs[i % R], pos, slot, cos, sin))
+
+    # logit penalty: every row active at repeat_penalty 1.1, a random
+    # history of 4096 tokens, windows of 64 and of all 4096 (two dependent
+    # global atomics per window token); the append rewrites one cell
+    ctx = 4096
+    hist = torch.randint(0, V, (B, ctx), device=dev).int()
+    counts = torch.zeros((B, V), dtype=torch.int32, device=dev)
+    lens = torch.full((B,), ctx, dtype=torch.int32, device=dev)
+    tok = torch.randint(0, V, (B,), device=dev).int()
+    rp = torch.full((B,), 1.1, device=dev)
+    zero = torch.zeros(B, device=dev)
+    for win in (64, ctx):
+        last_n = torch.full((B,), win, dtype=torch.int32, device=dev)
+        bench(f"logit_penalty w={win}", lambda i: hip.penalize_logits(
+            logits[i % R], hist, slot, lens, tok, last_n, rp, zero, zero,
+            counts))
+    assert not bool(counts.any())
 
 
 if __name__ == "__main__":
