@@ -15,7 +15,9 @@ batches whatever it is given).
 """
 from __future__ import annotations
 
+import gc
 import itertools
+import os
 import struct
 import time
 from dataclasses import dataclass, field
@@ -24,7 +26,7 @@ from typing import Callable, Dict, List, Optional
 import torch
 
 from ..ops.interface import AttnMeta
-from ..ops import interface as ops
+from ..ops import hip as _hip, interface as ops
 from .kvcache import PagedKVCache
 
 
@@ -122,10 +124,40 @@ class Sequence:
     finish_reason: Optional[str] = None
     cancelled: bool = False
     _chunk: int = 0                   # prompt tokens taken this step
+    noise_seed: int = 0               # in-graph Gumbel seed, set by submit
 
     @property
     def total_len(self) -> int:
         return len(self.prompt) + len(self.generated)
+
+
+def sampling_params(p):
+    """(temperature, top_k, top_p) of one request as the samplers take
+    them.  The one place a request's top_k = None and top_p = None or 0
+    become "off"."""
+    return p.temperature, p.top_k or 0, p.top_p if p.top_p else 1.0
+
+
+def sampling_rows(seqs, pad=0):
+    """(temperature, top_k, top_p, noise_seed) of every sequence, then of
+    `pad` bucket-padding rows (greedy, filters off)."""
+    for s in seqs:
+        yield (*sampling_params(s.params), s.noise_seed)
+    for _ in range(pad):
+        yield 0.0, 0, 1.0, 0
+
+
+def penalty_rows(seqs, pad=0):
+    """(penalty_n, repeat, presence, frequency penalty) of every sequence
+    as the penalty op takes them, then of `pad` padding rows.  Rows
+    without an active penalty, pad rows among them, carry n = 0: the
+    kernel appends their token and leaves their logits alone."""
+    for s in seqs:
+        p = s.params
+        yield (p.penalty_n, p.repeat_penalty, p.presence_penalty,
+               p.frequency_penalty)
+    for _ in range(pad):
+        yield 0, 1.0, 0.0, 0.0
 
 
 class LlamaEngine:
@@ -156,9 +188,8 @@ class LlamaEngine:
         # max_batch — measured stable across a 6-min soak after capture):
         # decode is ~7 kernels × n_layers of launches; replay collapses the
         # launch gaps (MI355X_MICROARCH "launches-baseline": ≈1.2 µs/boundary)
-        import os as _os
         self.use_graphs = (self.dev.type == "cuda"
-                           and _os.environ.get("OLLAMAMQ_NO_GRAPH") != "1")
+                           and os.environ.get("OLLAMAMQ_NO_GRAPH") != "1")
         # (batch bucket, class) for unpenalised batches, (bucket, class, 1)
         # for batches with a logit penalty (the penalty kernel in-graph)
         self._graphs: Dict[tuple, dict] = {}
@@ -174,7 +205,7 @@ class LlamaEngine:
         # late through a pinned-buffer/event ring while the GPU runs the
         # next step.  Drained on any batch-composition change.
         self.use_pipeline = (self.use_graphs
-                             and _os.environ.get("OLLAMAMQ_NO_PIPELINE")
+                             and os.environ.get("OLLAMAMQ_NO_PIPELINE")
                              != "1")
         self._pipe = None   # {"key": seq-id tuple, "inflight": (ev,buf,seqs)}
         # Decode batches are PADDED UP to a bucket size so the graph set
@@ -189,7 +220,7 @@ class LlamaEngine:
                                 if b <= max_batch})
         self._dummy_slot = -1
         # opt-in: capture the top-k/top-p tail in-graph (see _samp_class)
-        self._GRAPH_TOPK = _os.environ.get("OLLAMAMQ_GRAPH_TOPK") == "1"
+        self._GRAPH_TOPK = os.environ.get("OLLAMAMQ_GRAPH_TOPK") == "1"
 
     # -- submission --------------------------------------------------------
     def submit(self, prompt: List[int], params: GenParams,
@@ -256,15 +287,15 @@ class LlamaEngine:
             # mixed batch: every running sequence decodes one token AND
             # the new prompts prefill a chunk in the SAME forward — one
             # weight pass serves both, so admission never stalls decode
-            self._mixed_step(admitted)
+            self._prompt_step(admitted, self.running)
             # admitted seqs that finished prefill were moved into
-            # self.running by _mixed_step — don't postprocess them twice
+            # self.running by _prompt_step — don't postprocess them twice
             # (a double _finish would emit the done marker twice)
             finished = self._postprocess(
                 self.running + [s for s in admitted
                                 if s not in self.running])
         elif admitted:
-            self._prefill_step(admitted)
+            self._prompt_step(admitted, [])
             finished = self._postprocess(admitted)
         elif self.running:
             self._decode_step()
@@ -356,12 +387,14 @@ class LlamaEngine:
                 room -= 1
         return batch
 
-    def _mixed_step(self, batch: List[Sequence]):
+    def _prompt_step(self, batch: List[Sequence], running):
+        """One forward over the admitted prompts' chunks and, in the same
+        weight pass, one decode token for every sequence of `running`
+        ([] when nothing decodes)."""
         self._drain_pipe()   # decode rows need current host tokens
         # context-full sequences can't take another token; skip them this
         # step — _postprocess finishes them with reason "length"
-        dec = [s for s in self.running
-               if s.total_len < self.kv.max_ctx]
+        dec = [s for s in running if s.total_len < self.kv.max_ctx]
         token_list = [s.generated[-1] for s in dec]
         pos_list = [s.total_len - 1 for s in dec]
         q_lens = [1] * len(dec)
@@ -371,40 +404,50 @@ class LlamaEngine:
             token_list.extend(s.prompt[start:start + take])
             pos_list.extend(range(start, start + take))
             q_lens.append(take)
-        logits = self._forward(dec + batch, token_list, pos_list, q_lens,
-                               "mixed", n_decode=len(dec))
-        # sample decode rows + finishing-prefill rows
-        fin_rows = [len(dec) + i for i, s in enumerate(batch)
-                    if s.prefill_done + s._chunk == len(s.prompt)]
-        done_prefill = [batch[i - len(dec)] for i in fin_rows]
-        sample_rows = list(range(len(dec))) + fin_rows
-        toks = self._sample(dec + done_prefill, logits[sample_rows],
-                            **self._pen_kw(dec + done_prefill,
-                                           token_list[:len(dec)]
-                                           + [-1] * len(done_prefill)))
+        if dec:
+            logits = self._forward(dec + batch, token_list, pos_list, q_lens,
+                                   "mixed", n_decode=len(dec))
+        else:
+            logits = self._forward(batch, token_list, pos_list, q_lens,
+                                   "prefill")
+        # decode rows sample, and the prompts whose last chunk this was:
+        # only a sequence whose whole prompt is in KV emits a token
+        fin = [i for i, s in enumerate(batch)
+               if s.prefill_done + s._chunk == len(s.prompt)]
+        done_prefill = [batch[i] for i in fin]
+        seqs = dec + done_prefill
+        toks: List[int] = []
+        if seqs:
+            if len(seqs) < len(dec) + len(batch):
+                logits = logits[list(range(len(dec)))
+                                + [len(dec) + i for i in fin]]
+            if any(s.params.penalty_active for s in seqs):
+                logits = self._penalize(
+                    seqs, logits,
+                    token_list[:len(dec)] + [-1] * len(done_prefill))
+            toks = self._sample(seqs, logits)
         now = time.monotonic()
-        for s, tok in zip(dec, toks[:len(dec)]):
-            s.generated.append(int(tok))
-            self.tokens_out += 1
-            if s.on_token:
-                s.on_token(int(tok), False)
-        ptoks = toks[len(dec):]
+        for s, tok in zip(dec, toks):
+            self._emit(s, tok, now)
         for s in batch:
             s.prefill_done += s._chunk
-            if s.prefill_done == len(s.prompt):
-                s.first_token_at = now
-                s.state = "running"
-                self.waiting.remove(s)
-                self.running.append(s)
-                if s.params.max_tokens <= 0:
-                    # zero-token request (Ollama num_predict: 0): admit
-                    # without emitting; _postprocess finishes it this step
-                    continue
-                tok = ptoks[done_prefill.index(s)]
-                s.generated.append(int(tok))
-                self.tokens_out += 1
-                if s.on_token:
-                    s.on_token(int(tok), False)
+        for s, tok in zip(done_prefill, toks[len(dec):]):
+            s.first_token_at = now
+            s.state = "running"
+            self.waiting.remove(s)
+            self.running.append(s)
+            # a zero-token request (Ollama num_predict: 0) is admitted
+            # without emitting; _postprocess finishes it this step
+            if s.params.max_tokens > 0:
+                self._emit(s, tok, now)
+
+    def _emit(self, seq, tok, now):
+        seq.generated.append(int(tok))
+        self.tokens_out += 1
+        if seq.first_token_at is None:
+            seq.first_token_at = now
+        if seq.on_token:
+            seq.on_token(int(tok), False)
 
     def _build_meta(self, seqs, q_lens, mode, n_decode=0) -> AttnMeta:
         dev = self.dev
@@ -446,105 +489,46 @@ class LlamaEngine:
         pen_tok[i] is row i's input token this step (appended to the
         history at its own position) or -1 for a row finishing its
         prefill, whose prompt is in the history already."""
+        if not logits.is_contiguous():
+            logits = logits.contiguous()
         dev = logits.device
+        last_n, rp, pp, fp = zip(*penalty_rows(seqs))
         ints = torch.tensor(
             [[s.slot for s in seqs],
              [self.kv.seq_lens[s.slot] for s in seqs],
-             list(pen_tok),
-             [s.params.penalty_n for s in seqs]],
-            dtype=torch.int32).to(dev)
-        flts = torch.tensor(
-            [[s.params.repeat_penalty for s in seqs],
-             [s.params.presence_penalty for s in seqs],
-             [s.params.frequency_penalty for s in seqs]],
-            dtype=torch.float32).to(dev)
+             list(pen_tok), last_n], dtype=torch.int32).to(dev)
+        flts = torch.tensor([rp, pp, fp], dtype=torch.float32).to(dev)
         return ops.penalize_logits(
             logits, self._hist, ints[0], ints[1], ints[2], ints[3],
             flts[0], flts[1], flts[2], self._counts)
 
-    @staticmethod
-    def _pen_kw(seqs, pen_tok, penalized=False):
-        """_sample's penalty arguments; none for an unpenalised batch,
-        whose call stays _sample(seqs, logits)."""
-        if not any(s.params.penalty_active for s in seqs):
-            return {}
-        return {"pen_tok": pen_tok, "penalized": penalized}
-
-    def _sample(self, seqs, logits, pen_tok=None, penalized=False):
-        """Sample one token per row.  Rows of a batch with an active logit
-        penalty are penalised here first (pen_tok: see _penalize) unless
-        `penalized` says the logits already are — a penalised graph
-        entry's logits come out of the in-graph kernel, and a second
-        application would penalise twice."""
-        if not penalized and any(s.params.penalty_active for s in seqs):
-            if not logits.is_contiguous():
-                logits = logits.contiguous()
-            logits = self._penalize(seqs, logits, pen_tok)
+    def _sample(self, seqs, logits):
+        """Sample one token per row.  A batch with an active logit penalty
+        reaches this penalised: in-graph for a penalised graph entry, by
+        the step's own _penalize call for every other source of logits."""
         dev = logits.device
-        temps = torch.tensor([s.params.temperature for s in seqs],
-                             dtype=torch.float32, device=dev)
         # per-request top_k/top_p: each row is filtered by its own params
         # (vectorized in ops.sample — mixed batches never bleed)
-        top_k = torch.tensor([s.params.top_k or 0 for s in seqs],
-                             dtype=torch.long, device=dev)
-        top_p = torch.tensor(
-            [s.params.top_p if s.params.top_p else 1.0 for s in seqs],
-            dtype=torch.float32, device=dev)
-        toks = ops.sample(logits, temps, top_k, top_p, self._gen)
+        temps, top_k, top_p, _ = zip(*sampling_rows(seqs))
+        toks = ops.sample(
+            logits, torch.tensor(temps, dtype=torch.float32, device=dev),
+            torch.tensor(top_k, dtype=torch.long, device=dev),
+            torch.tensor(top_p, dtype=torch.float32, device=dev), self._gen)
         out = toks.tolist()
         # per-request `seed` (Ollama options.seed): stochastic rows with a
         # seed re-sample alone under a generator keyed (seed, step-index)
         # so the same request reproduces regardless of batch composition
         for i, s in enumerate(seqs):
-            p = s.params
-            if p.seed is not None and p.temperature > 0:
-                g = torch.Generator(device=logits.device)
+            if s.params.seed is not None and temps[i] > 0:
+                g = torch.Generator(device=dev)
                 g.manual_seed(host_seed_key(
                     s.noise_seed, len(s.generated) + len(s.prompt)))
                 t = ops.sample(logits[i:i + 1],
-                               torch.tensor([p.temperature],
-                                            dtype=torch.float32,
-                                            device=logits.device),
-                               p.top_k or 0, p.top_p or 1.0, g)
+                               torch.tensor([temps[i]], dtype=torch.float32,
+                                            device=dev),
+                               top_k[i], top_p[i], g)
                 out[i] = int(t[0])
         return out
-
-    def _prefill_step(self, batch: List[Sequence]):
-        self._drain_pipe()
-        token_list, pos_list, q_lens = [], [], []
-        for s in batch:
-            take = s._chunk
-            start = s.prefill_done
-            token_list.extend(s.prompt[start:start + take])
-            pos_list.extend(range(start, start + take))
-            q_lens.append(take)
-        logits = self._forward(batch, token_list, pos_list, q_lens, "prefill")
-        # Only sequences whose whole prompt is now in KV emit a token.
-        rows = [i for i, s in enumerate(batch)
-                if s.prefill_done + s._chunk == len(s.prompt)]
-        done_prefill = [batch[i] for i in rows]
-        toks: List[int] = []
-        if done_prefill:
-            sub = logits if len(rows) == len(batch) else logits[rows]
-            toks = self._sample(done_prefill, sub,
-                                **self._pen_kw(done_prefill,
-                                               [-1] * len(done_prefill)))
-        for s in batch:
-            s.prefill_done += s._chunk
-            if s.prefill_done == len(s.prompt):
-                s.first_token_at = time.monotonic()
-                s.state = "running"
-                self.waiting.remove(s)
-                self.running.append(s)
-                if s.params.max_tokens <= 0:
-                    # zero-token request (Ollama num_predict: 0): admit
-                    # without emitting; _postprocess finishes it this step
-                    continue
-                tok = toks[done_prefill.index(s)]
-                s.generated.append(int(tok))
-                self.tokens_out += 1
-                if s.on_token:
-                    s.on_token(int(tok), False)
 
     def _samp_class(self, seqs) -> int:
         """0 = all greedy (argmax tail), 1 = temperature-only mix (Gumbel
@@ -562,17 +546,16 @@ class LlamaEngine:
         host (exact, full vocabulary) with the forward still graphed."""
         k, capped = 0, True
         for s in seqs:
-            p = s.params
-            if p.temperature > 0:
-                if (p.top_k or 0) > 0 or (p.top_p if p.top_p else 1.0) \
-                        < 1.0:
+            temp, top_k, top_p = sampling_params(s.params)
+            if temp > 0:
+                if top_k > 0 or top_p < 1.0:
                     k = 2
                 else:
                     k = max(k, 1)
                 # the class-2 tail sees the top-256 candidates only: it
                 # is exact iff every stochastic row's support lies inside
                 # them (ops/hip.py sample: capped_ok)
-                capped &= 0 < (p.top_k or 0) <= 256
+                capped &= 0 < top_k <= 256
         if k == 2:
             return 2 if self._GRAPH_TOPK and capped else 3
         return k
@@ -648,37 +631,26 @@ class LlamaEngine:
         bufs["slot"].copy_(staged[2])
         bufs["lens"].copy_(staged[3])
         bufs["adv"].copy_(staged[4])
+
+        def put(key, col, dtype):
+            bufs[key].copy_(torch.tensor(col, dtype=dtype)
+                            .to(self.dev, non_blocking=True))
+
         if entry["pen"]:
-            # rows without an active penalty, pad rows among them, carry
-            # last_n = 0: the kernel appends their token and leaves their
-            # logits alone
-            bufs["last_n"].copy_(torch.tensor(
-                [s.params.penalty_n for s in seqs] + [0] * pad,
-                dtype=torch.int32).to(self.dev, non_blocking=True))
-            pen = torch.tensor(
-                [[s.params.repeat_penalty for s in seqs] + [1.0] * pad,
-                 [s.params.presence_penalty for s in seqs] + [0.0] * pad,
-                 [s.params.frequency_penalty for s in seqs] + [0.0] * pad],
-                dtype=torch.float32).to(self.dev, non_blocking=True)
+            last_n, rp, pp, fp = zip(*penalty_rows(seqs, pad))
+            put("last_n", last_n, torch.int32)
+            pen = torch.tensor([rp, pp, fp], dtype=torch.float32) \
+                .to(self.dev, non_blocking=True)
             bufs["rp"].copy_(pen[0])
             bufs["pp"].copy_(pen[1])
             bufs["fp"].copy_(pen[2])
         if entry["klass"] >= 1:
-            bufs["temps"].copy_(torch.tensor(
-                [s.params.temperature for s in seqs] + [0.0] * pad,
-                dtype=torch.float32).to(self.dev, non_blocking=True))
-            bufs["seeds"].copy_(torch.tensor(
-                [getattr(s, "noise_seed", 1234) for s in seqs]
-                + [0] * pad,
-                dtype=torch.int64).to(self.dev, non_blocking=True))
+            temps, top_k, top_p, seeds = zip(*sampling_rows(seqs, pad))
+            put("temps", temps, torch.float32)
+            put("seeds", seeds, torch.int64)
         if entry["klass"] == 2:
-            bufs["topk"].copy_(torch.tensor(
-                [s.params.top_k or 0 for s in seqs] + [0] * pad,
-                dtype=torch.int64).to(self.dev, non_blocking=True))
-            bufs["topp"].copy_(torch.tensor(
-                [s.params.top_p if s.params.top_p else 1.0
-                 for s in seqs] + [1.0] * pad,
-                dtype=torch.float32).to(self.dev, non_blocking=True))
+            put("topk", top_k, torch.int64)
+            put("topp", top_p, torch.float32)
 
     def _graph_tail(self, entry, logits):
         """The in-graph sampling tail: class 0 = greedy argmax; class 1 =
@@ -686,9 +658,9 @@ class LlamaEngine:
         greedy rows ride the same kernel with T<=0), noise keyed by
         (per-seq seed, kv length) so replays draw fresh randomness with
         no host RNG; class 2 = per-row top-k/top-p over the top-256
-        candidates with their full-vocabulary probabilities (capturable
-        torch ops; every stochastic row has 0 < top_k <= 256, see
-        _samp_class), then exact Gumbel-max on the filtered set, noise
+        candidates with their full-vocabulary probabilities (ops/hip.py
+        candidate_filter: capturable torch ops; every stochastic row has
+        0 < top_k <= 256, see _samp_class), then exact Gumbel-max on the filtered set, noise
         keyed by the candidate's rank; greedy rows take the HIP argmax
         of the full row.
 
@@ -700,29 +672,11 @@ class LlamaEngine:
         under mixed sampled serving (r02 stress)."""
         bufs = entry["bufs"]
         if entry["klass"] == 1:
-            from ..ops import hip as _hip
             return _hip.sample_gumbel(logits, bufs["temps"],
                                       bufs["seeds"], bufs["lens"])
         if entry["klass"] == 2:
-            from ..ops import hip as _hip
-            C = min(256, logits.shape[1])
-            lf = logits.float()
-            greedy = bufs["temps"] <= 0
-            t = torch.where(greedy, torch.ones_like(bufs["temps"]),
-                            bufs["temps"]).unsqueeze(1)
-            v, idx = torch.topk(lf, C, dim=-1)
-            # full-vocabulary logsumexp, as ops/hip.py sample: the
-            # top-p mass is measured on the true probabilities, not on
-            # the candidates renormalised
-            lse = torch.logsumexp(lf / t, dim=-1, keepdim=True)
-            p = torch.exp(v / t - lse)
-            ar = torch.arange(C, device=logits.device)
-            keep = ar.unsqueeze(0) < \
-                bufs["topk"].clamp(min=1, max=C).unsqueeze(1)
-            cum = p.cumsum(dim=-1)
-            tpc = bufs["topp"].unsqueeze(1)
-            keep &= ((cum - p) < tpc) | (tpc >= 1.0)
-            keep[:, 0] = True
+            v, idx, _, keep, greedy = _hip.candidate_filter(
+                logits, bufs["temps"], bufs["topk"], bufs["topp"])
             vm = v.masked_fill(~keep, float("-inf")).bfloat16()
             ci = _hip.sample_gumbel(vm.contiguous(), bufs["temps"],
                                     bufs["seeds"], bufs["lens"])
@@ -755,7 +709,6 @@ class LlamaEngine:
             # issues a hipFree, which is illegal while a stream is
             # capturing and aborts the process (observed under the full
             # GPU suite) — flush pending frees first, then hold GC off.
-            import gc
             gc.collect()
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
@@ -792,13 +745,6 @@ class LlamaEngine:
             entry["graph"] = g
         entry["graph"].replay()
         return entry["logits"]
-
-    def _decode_forward_graphed(self, seqs, token_list, pos_list,
-                                pen=False):
-        entry = self._graph_entry(self._bucket(len(seqs)),  # class-0:
-                                  0, pen)                   # host samples
-        self._fill_bufs(entry, seqs, token_list, pos_list)
-        return self._graph_replay(entry)[:len(seqs)]
 
     def warm_graphs(self, sizes=None, classes=None, penalty=False):
         """Pre-capture the decode graphs for EVERY (bucket, sampling
@@ -865,23 +811,20 @@ class LlamaEngine:
         if self.use_graphs:
             for s in seqs:
                 self.kv.ensure(s.slot, self.kv.seq_lens[s.slot] + 1)
-            logits = self._decode_forward_graphed(seqs, token_list,
-                                                  pos_list, pen)
+            # a class-0 entry: the host samples.  A penalised entry's
+            # logits come out of the graph penalised already
+            entry = self._graph_entry(self._bucket(len(seqs)), 0, pen)
+            self._fill_bufs(entry, seqs, token_list, pos_list)
+            logits = self._graph_replay(entry)[:len(seqs)]
         else:
             logits = self._forward(seqs, token_list, pos_list, q_lens,
                                    "decode")
-        # a penalised graph entry's logits are penalised already
-        toks = self._sample(seqs, logits,
-                            **self._pen_kw(seqs, token_list,
-                                           pen and self.use_graphs))
+            if pen:
+                logits = self._penalize(seqs, logits, token_list)
+        toks = self._sample(seqs, logits)
         now = time.monotonic()
         for s, tok in zip(seqs, toks):
-            s.generated.append(int(tok))
-            self.tokens_out += 1
-            if s.first_token_at is None:
-                s.first_token_at = now
-            if s.on_token:
-                s.on_token(int(tok), False)
+            self._emit(s, tok, now)
 
     # -- pipelined decode --------------------------------------------------
     def _decode_step_pipelined(self, seqs):
@@ -930,14 +873,8 @@ class LlamaEngine:
         toks = pinned.tolist()
         now = time.monotonic()
         for s, tok in zip(seqs, toks):
-            if s.state != "running":   # finished/cancelled after issue
-                continue
-            s.generated.append(int(tok))
-            self.tokens_out += 1
-            if s.first_token_at is None:
-                s.first_token_at = now
-            if s.on_token:
-                s.on_token(int(tok), False)
+            if s.state == "running":   # not finished/cancelled after issue
+                self._emit(s, tok, now)
 
     def _postprocess(self, seqs) -> List[Sequence]:
         finished = []

@@ -863,6 +863,46 @@ def penalize_logits(logits, hist, slot, lens, tok, last_n, rp, pp, fp,
     return logits
 
 
+def candidate_filter(logits, temps, top_k, top_p):
+    """The per-row top-k/top-p filter over the top-C candidates, C =
+    min(256, V); temps, top_k (int64) and top_p are [B] tensors.  Returns
+    (v, idx, p, keep, greedy); the first four are [B, C] in descending
+    order: the raw fp32 logits, their token ids, their FULL-vocabulary
+    probabilities exp(v/T - logsumexp(l/T)) and the mask of the candidates
+    a row keeps.  Greedy rows (T <= 0) are filtered at T = 1; `greedy` is
+    that [B] row mask, handed back so that a captured caller launches
+    nothing a second time.  Exact for a row with
+    0 < top_k <= C: its nucleus is a subset of its top-k, and the top-p
+    mass is measured on the true probabilities, not on the candidates
+    renormalised.
+
+    The topk is taken over the raw logits, not over l / T: the selected
+    values, v / T, the logsumexp and p are bit-equal either way (the same
+    fp32 division on the same elements); only the order among candidates
+    whose l / T round to one fp32 value while their l differ could
+    change, and topk promises no order among equals in either form.
+
+    Shared by sample() and the engine's captured class-2 tail, so it must
+    stay capturable: torch ops only, no host synchronisation, no
+    data-dependent Python branch, nothing from _cached."""
+    C = min(256, logits.shape[1])
+    lf = logits.float()
+    greedy = temps <= 0
+    t = torch.where(greedy, torch.ones_like(temps), temps).unsqueeze(1)
+    v, idx = torch.topk(lf, C, dim=-1)
+    lse = torch.logsumexp(lf / t, dim=-1, keepdim=True)
+    p = torch.exp(v / t - lse)
+    ar = torch.arange(C, device=logits.device)
+    keep = ar.unsqueeze(0) < top_k.clamp(min=1, max=C).unsqueeze(1)
+    cum = p.cumsum(dim=-1)
+    # top_p >= 1 is off (as ref.sample): at a low temperature the fp32
+    # cumsum is 1.0 from rank 0 on
+    tpc = top_p.unsqueeze(1)
+    keep &= ((cum - p) < tpc) | (tpc >= 1.0)
+    keep[:, 0] = True
+    return v, idx, p, keep, greedy
+
+
 def sample(logits, temperature, top_k, top_p, generator=None):
     if torch.is_tensor(temperature):
         all_greedy = bool((temperature <= 0).all())
@@ -878,39 +918,26 @@ def sample(logits, temperature, top_k, top_p, generator=None):
         return out.long()
     # stochastic host path.  When every stochastic row carries
     # 0 < top_k <= 256 the sampling is EXACT over the top-256 candidates
-    # (its nucleus is a subset of its top-k; probabilities use a
-    # full-vocabulary logsumexp, so the top-p mass cut is the true one)
-    # and costs a topk + tiny multinomial instead of the full-vocab sort
-    # (~0.5 ms/step at V=128256).  Anything else falls back to the
-    # fp32 reference (exact, sort-based).
+    # (candidate_filter) and costs a topk + tiny multinomial instead of
+    # the full-vocab sort (~0.5 ms/step at V=128256).  Anything else falls
+    # back to the fp32 reference (exact, sort-based).  Scalar parameters
+    # are taken as given (top_k 0 and top_p >= 1 are off); a request's
+    # None / 0 are mapped by the engine, once (engine.py sampling_params).
     B, V = logits.shape
     dev = logits.device
     if not torch.is_tensor(temperature):
         temperature = torch.full((B,), float(temperature), device=dev)
-    tk = top_k if torch.is_tensor(top_k) else torch.full(
-        (B,), int(top_k or 0), dtype=torch.long, device=dev)
-    tp = top_p if torch.is_tensor(top_p) else torch.full(
-        (B,), float(top_p if top_p else 1.0), device=dev)
+    tk, tp = top_k, top_p
+    if not torch.is_tensor(tk):
+        tk = torch.full((B,), int(tk), dtype=torch.long, device=dev)
+    if not torch.is_tensor(tp):
+        tp = torch.full((B,), float(tp), device=dev)
     tk = tk.long()
     stoch = temperature > 0
-    C = min(256, V)
-    capped_ok = bool(((tk > 0) & (tk <= C) | ~stoch).all())
+    capped_ok = bool(((tk > 0) & (tk <= min(256, V)) | ~stoch).all())
     if not capped_ok:
         return ref.sample(logits, temperature, tk, tp, generator)
-    l = logits.float()
-    t = torch.where(stoch, temperature, torch.ones_like(temperature))
-    lt = l / t.unsqueeze(1)
-    v, idx = torch.topk(lt, C, dim=-1)
-    lse = torch.logsumexp(lt, dim=-1, keepdim=True)
-    p = torch.exp(v - lse)                      # exact full-vocab probs
-    ar = torch.arange(C, device=dev)
-    keep = ar.unsqueeze(0) < tk.clamp(min=1, max=C).unsqueeze(1)
-    cum = p.cumsum(dim=-1)
-    # top_p >= 1 is off (as ref.sample): at a low temperature the fp32
-    # cumsum is 1.0 from rank 0 on
-    tpc = tp.unsqueeze(1)
-    keep &= ((cum - p) < tpc) | (tpc >= 1.0)
-    keep[:, 0] = True
+    _, idx, p, keep, _ = candidate_filter(logits, temperature, tk, tp)
     pm = p * keep
     pick = torch.multinomial(pm / pm.sum(-1, keepdim=True), 1,
                              generator=generator).squeeze(1)
@@ -918,7 +945,7 @@ def sample(logits, temperature, top_k, top_p, generator=None):
     if bool(stoch.all()):
         return out_s
     # greedy rows override with the true argmax
-    return torch.where(stoch, out_s, l.argmax(-1))
+    return torch.where(stoch, out_s, logits.float().argmax(-1))
 
 
 def decode_pure(cache, layer, meta, split, chunk=64):

@@ -455,8 +455,12 @@ def budget(name):
     measured on the fp32 CPU reference: 4 x its worst relative error of a
     kept probability (floored at 2^-20), and 4 x its worst fp32 cumsum
     error."""
+    return case_budget(case(name))
+
+
+def case_budget(c):
+    """budget() of a case that is not in the shared list."""
     from ollamamq_amd.ops import reference as ref
-    c = case(name)
     toks, seen, _ = run_captured(ref.sample, c, "first")
     worst = 0.0
     for r, (p, _) in seen.items():

@@ -60,7 +60,7 @@ def measure(eng, cfg, users, label, n=30, **pen):
     logits = entry["logits"][:users]
     t0 = time.perf_counter()
     for _ in range(n):
-        eng._sample(eng.running, logits, penalized=True)
+        eng._sample(eng.running, logits)
     torch.cuda.synchronize()
     sample = (time.perf_counter() - t0) / n
 
