@@ -39,11 +39,24 @@ def build_kernels(force=False):
     if not force and _newer(out, *srcs, *hdrs):
         print(f"kernels up to date: {out}")
         return out
-    _run([
-        "hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17",
-        "-shared", "-fPIC", *srcs, "-o", out,
-    ])
+    base = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
+    # sources with flags of their own are compiled to objects first; the
+    # rest go through the one command they always did, flags unchanged
+    objs = []
+    for s in srcs:
+        extra = _KERNEL_FLAGS.get(os.path.basename(s))
+        if extra:
+            objs.append(s[:-len(".hip")] + ".o")
+            _run([*base, *extra, "-c", s, "-o", objs[-1]])
+    plain = [s for s in srcs if os.path.basename(s) not in _KERNEL_FLAGS]
+    # objects before the sources: hipcc's "-x hip" holds for what follows it
+    _run([*base, "-shared", *objs, *plain, "-o", out])
     return out
+
+
+# no packed fp32 arithmetic (v_pk_*_f32) in kernels written from here on
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+_KERNEL_FLAGS = {"topk_sample.hip": _NO_PK_F32}
 
 
 def build_dispatcher(force=False):

@@ -125,3 +125,28 @@ DEV int64_t paged_kv_row(const int* page_table, int slot, int max_pages,
     const int pg = page_table[(int64_t)slot * max_pages + pos / page];
     return (((int64_t)pg * KVH + head) * page + pos % page) * 128;
 }
+
+// ---------------------------------------------------------------------------
+// Counter-based sampler noise, shared by the Gumbel sampler (kernels.hip)
+// and the top-k/top-p sampler (topk_sample.hip).
+// ---------------------------------------------------------------------------
+// u = (top 23 bits + 0.5) * 2^-23: 2m + 1 < 2^24, so the sum and the
+// scaling are exact in fp32 and u spans [2^-24, 1 - 2^-24].  (24 bits + 0.5
+// is a rounding tie above 2^23 and reaches u == 1, i.e. g = +inf, which
+// wins the argmax whatever its logit.)  The Gumbel noise is therefore
+// finite, within [-2.82, 16.64], for every (seed, ctr, v).
+DEV float u01_hash(uint64_t key) {
+    key ^= key >> 33; key *= 0xff51afd7ed558ccdULL;
+    key ^= key >> 33; key *= 0xc4ceb9fe1a85ec53ULL;
+    key ^= key >> 33;
+    return ((float)(key >> 41) + 0.5f) * (1.0f / 8388608.0f);
+}
+
+DEV float gumbel_of(uint64_t seed, uint64_t ctr, int v,
+                    const float* noise, int64_t noff) {
+    const float u = noise ? noise[noff + v]
+                          : u01_hash((seed * 0x9E3779B97F4A7C15ULL)
+                                     ^ (ctr * 0xD1B54A32D192ED03ULL)
+                                     ^ (uint64_t)v);
+    return -__logf(-__logf(u));
+}

@@ -219,8 +219,12 @@ class LlamaEngine:
                                  48, 64, 96, 128, max_batch)
                                 if b <= max_batch})
         self._dummy_slot = -1
-        # opt-in: capture the top-k/top-p tail in-graph (see _samp_class)
-        self._GRAPH_TOPK = os.environ.get("OLLAMAMQ_GRAPH_TOPK") == "1"
+        # opt-in: capture the top-k/top-p tail in-graph (see _samp_class):
+        # "1" = the torch candidate tail, "hip" = the one-call HIP tail
+        # (ops/hip.py sample_topk), which launches no torch op
+        topk_env = os.environ.get("OLLAMAMQ_GRAPH_TOPK")
+        self._GRAPH_TOPK = topk_env in ("1", "hip")
+        self._TOPK_HIP = topk_env == "hip"
 
     # -- submission --------------------------------------------------------
     def submit(self, prompt: List[int], params: GenParams,
@@ -543,7 +547,10 @@ class LlamaEngine:
         or without the fused chain (tools/repro_sampled.py WORKLOAD=topk)
         — an unresolved interaction between the captured topk and the
         serving graph set.  Until root-caused, top-k/p rows sample on the
-        host (exact, full vocabulary) with the forward still graphed."""
+        host (exact, full vocabulary) with the forward still graphed.
+        OLLAMAMQ_GRAPH_TOPK=hip captures class 2 too, with the HIP tail
+        (no torch op in it); it stays opt-in until it has had a serving
+        soak of its own."""
         k, capped = 0, True
         for s in seqs:
             temp, top_k, top_p = sampling_params(s.params)
@@ -662,7 +669,9 @@ class LlamaEngine:
         candidate_filter: capturable torch ops; every stochastic row has
         0 < top_k <= 256, see _samp_class), then exact Gumbel-max on the filtered set, noise
         keyed by the candidate's rank; greedy rows take the HIP argmax
-        of the full row.
+        of the full row.  With OLLAMAMQ_GRAPH_TOPK=hip class 2 is one
+        call of ops/hip.py sample_topk instead: the same candidates,
+        filter and rank-keyed noise in two HIP launches.
 
         This MUST also run once EAGERLY in the pre-capture warmup: the
         samplers cache split-scratch buffers (ops/hip.py _scratch), and a
@@ -674,6 +683,12 @@ class LlamaEngine:
         if entry["klass"] == 1:
             return _hip.sample_gumbel(logits, bufs["temps"],
                                       bufs["seeds"], bufs["lens"])
+        if entry["klass"] == 2 and self._TOPK_HIP:
+            # selection, filter, noise and pick in two HIP launches; greedy
+            # rows take rank 0, the lowest-index maximum, in the same call
+            return _hip.sample_topk(logits, bufs["temps"], bufs["topk"],
+                                    bufs["topp"], bufs["seeds"],
+                                    bufs["lens"])
         if entry["klass"] == 2:
             v, idx, _, keep, greedy = _hip.candidate_filter(
                 logits, bufs["temps"], bufs["topk"], bufs["topp"])

@@ -60,6 +60,8 @@ def _signatures():
                                   vp, vp, vp, i, i, i, i, i, vp, vp],
         "logit_penalty_bf16": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                i, i, i, i, vp],
+        "sample_topk_bf16": [vp, vp, vp, vp, vp, vp, vp, i, i,
+                             vp, vp, i, vp, vp, vp, vp],
     }
 
 
@@ -861,6 +863,71 @@ def penalize_logits(logits, hist, slot, lens, tok, last_n, rp, pp, fp,
         _p(rp), _p(pp), _p(fp), _p(counts), B, V, hist.shape[1],
         hist.shape[0], _stream()), "logit_penalty")
     return logits
+
+
+TOPK_C = 256       # candidates per row of sample_topk (topk_sample.hip TOPC)
+
+
+def sample_topk(logits, temps, top_k, top_p, seeds, ctrs, out=None,
+                cand=None):
+    """Per-row top-k/top-p sampling in HIP (topk_sample.hip; contract in
+    docs/KERNELS.md): the C = min(256, V) largest logits of each row in
+    order (value descending, token id ascending among equals), filtered
+    by candidate_filter's rule on their full-vocabulary probabilities,
+    then Gumbel-max among the kept ranks with the noise keyed by (seed,
+    counter, rank).  Rows with temps <= 0 take rank 0, the lowest-index
+    maximum.  Returns int32 [B] tokens.
+
+    logits [B, V] bf16; temps, top_p fp32, top_k, seeds int64, ctrs int32
+    vectors of at least B rows (the engine's bufs as they are, no cast).
+    cand: optional (vals fp32 [>= B, 256], ids int32 [>= B, 256], pick
+    int32 [>= B]) that the kernel fills: the ranks' token ids, their raw
+    values (-inf where a stochastic row filters the rank out) and the
+    picked rank; columns >= C are left alone.  Two launches; the only
+    allocations are `out` when not given and, on the first call of a (B,
+    device), the slice scratch, so the eager warm-up of the engine's tail
+    must come before a capture as for the other samplers."""
+    if logits.dim() != 2 or logits.dtype != torch.bfloat16 \
+            or not logits.is_contiguous() or not logits.is_cuda \
+            or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError("sample_topk: logits must be a contiguous, "
+                         "non-empty [B, V] bf16 tensor on the GPU")
+    B, V = logits.shape
+    dev = logits.device
+    vecs = [("temps", temps, torch.float32), ("top_k", top_k, torch.int64),
+            ("top_p", top_p, torch.float32), ("seeds", seeds, torch.int64),
+            ("ctrs", ctrs, torch.int32)]
+    if out is not None:
+        vecs.append(("out", out, torch.int32))
+    if cand is not None:
+        vals, ids, pick = cand
+        vecs.append(("cand pick", pick, torch.int32))
+        for name, t, dt in (("vals", vals, torch.float32),
+                            ("ids", ids, torch.int32)):
+            if t.dim() != 2 or t.dtype != dt or not t.is_contiguous() \
+                    or t.device != dev or t.shape[0] < B \
+                    or t.shape[1] != TOPK_C:
+                raise ValueError(f"sample_topk: cand {name} must be a "
+                                 f"contiguous {dt} [>= {B}, {TOPK_C}] "
+                                 "tensor on the logits' device")
+    for name, t, dt in vecs:
+        if t.dtype != dt or t.dim() != 1 or t.shape[0] < B \
+                or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"sample_topk: {name} must be a contiguous "
+                             f"{dt} vector of at least {B} rows on the "
+                             "logits' device")
+    if out is None:
+        out = torch.empty(B, dtype=torch.int32, device=dev)
+    sp = min(32, max(1, 768 // B))          # as _splitv_scratch
+    hist1, part = _cached(("topk", B, sp, str(dev)), lambda: (
+        torch.empty(B * sp * 256, dtype=torch.int32, device=dev),
+        torch.empty(B * sp * 2, dtype=torch.float32, device=dev)))
+    cv, ci, cp = cand if cand is not None else (None, None, None)
+    _check(_lib.sample_topk_bf16(
+        _p(out), _p(logits), _p(temps), _p(top_k), _p(top_p), _p(seeds),
+        _p(ctrs), B, V, _p(hist1), _p(part), sp, _p(cv), _p(ci), _p(cp),
+        _stream()), "sample_topk")
+    return out
 
 
 def candidate_filter(logits, temps, top_k, top_p):

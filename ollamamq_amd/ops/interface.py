@@ -277,6 +277,17 @@ def penalize_logits(logits, hist, slot, lens, tok, last_n, rp, pp, fp,
                                rp, pp, fp, counts)
 
 
+def sample_topk(logits, temps, top_k, top_p, seeds, ctrs, out=None,
+                cand=None):
+    """Top-k/top-p selection, filter and Gumbel-max pick in two HIP
+    launches (GPU only; the engine's class-2 tail under
+    OLLAMAMQ_GRAPH_TOPK=hip).  See ops/hip.py sample_topk."""
+    from . import hip
+    hip.require()
+    return hip.sample_topk(logits, temps, top_k, top_p, seeds, ctrs,
+                           out=out, cand=cand)
+
+
 def sample(logits, temperature, top_k, top_p, generator=None):
     # Sampler: torch ops compose on-GPU; custom fused kernel in ops/hip.py
     # handles the greedy + temperature paths.

@@ -1,5 +1,5 @@
 """Decode-shape microbench for the small per-step kernels (rmsnorm,
-swiglu, rope_append, argmax, logit penalty): isolates each op at batch B with cold
+swiglu, rope_append, argmax, logit penalty, top-k/top-p sampling): isolates each op at batch B with cold
 activations (cycled buffers) to see how far each sits above its
 latency floor.  Run on a GPU box: python tools/perf_elementwise.py [B]
 """
@@ -79,6 +79,30 @@ def main():
             logits[i % R], hist, slot, lens, tok, last_n, rp, zero, zero,
             counts))
     assert not bool(counts.any())
+
+    # top-k/top-p sampling, every row at temperature 0.8, top_k 40, top_p
+    # 0.9: the HIP op (two launches) beside the torch class-2 tail
+    # (candidate_filter + masked Gumbel + gather + argmax, as
+    # engine._graph_tail runs it), both eager on fresh randn logits
+    temps = torch.full((B,), 0.8, device=dev)
+    topk = torch.full((B,), 40, dtype=torch.int64, device=dev)
+    topp = torch.full((B,), 0.9, device=dev)
+    seeds = torch.arange(B, dtype=torch.int64, device=dev)
+    out = torch.empty(B, dtype=torch.int32, device=dev)
+    logits = [torch.randn(B, V, device=dev).bfloat16() for _ in range(R)]
+
+    def torch_tail(i):
+        lg = logits[i % R]
+        v, idx, _, keep, greedy = hip.candidate_filter(lg, temps, topk, topp)
+        vm = v.masked_fill(~keep, float("-inf")).bfloat16()
+        ci = hip.sample_gumbel(vm.contiguous(), temps, seeds, lens)
+        tok = idx.gather(1, ci.long().unsqueeze(1)).squeeze(1).int()
+        return torch.where(greedy, hip.sample(lg, 0.0, 0, 1.0).int(), tok)
+
+    for rep in range(3):
+        bench(f"sample_topk hip #{rep}", lambda i: hip.sample_topk(
+            logits[i % R], temps, topk, topp, seeds, lens, out=out))
+        bench(f"class-2 torch tail #{rep}", torch_tail)
 
 
 if __name__ == "__main__":

@@ -4,12 +4,17 @@ Runs the 8B engine to steady state, then times (a) full engine.step()
 iterations and (b) bare graph replays of the same captured step — the gap
 is Python/host bookkeeping that the GPU waits on.
 
-  python tools/perf_step.py [model] [users] [--penalty]
+  python tools/perf_step.py [model] [users] [--penalty] [--topk]
 
 --penalty measures the same step a second time in the same process with
 every row at repeat_penalty 1.1, repeat_last_n 64 (the penalised graph:
 the logit-penalty kernel between the forward and the sampling tail) and
 prints the difference.
+
+--topk measures, in the same process, every row at temperature 0.8, top_k 40,
+top_p 0.9 twice: as a class-3 step (graphed forward, host sampling: the
+default) and as a class-2 step with the HIP tail (OLLAMAMQ_GRAPH_TOPK=hip:
+ops.hip.sample_topk inside the graph), and prints both.
 """
 import os
 import sys
@@ -22,7 +27,7 @@ from ollamamq_amd.models import LlamaModel, PRESETS
 from ollamamq_amd.engine import LlamaEngine, PagedKVCache, GenParams
 
 
-def measure(eng, cfg, users, label, n=30, **pen):
+def measure(eng, cfg, users, label, n=30, klass=0, **pen):
     g = torch.Generator().manual_seed(3)
     for _ in range(users):
         eng.submit(torch.randint(0, cfg.vocab, (512,), generator=g).tolist(),
@@ -41,7 +46,8 @@ def measure(eng, cfg, users, label, n=30, **pen):
     torch.cuda.synchronize()
     full = (time.perf_counter() - t0) / n
 
-    key = (eng._bucket(users), 0) + ((1,) if pen else ())
+    key = (eng._bucket(users), klass) + (
+        (1,) if "repeat_penalty" in pen else ())
     entry = eng._graphs.get(key)
     assert entry is not None and entry["graph"] is not None, \
         (key, sorted(eng._graphs))
@@ -96,6 +102,15 @@ def main():
                                  repeat_penalty=1.1, repeat_last_n=64)
         print(f"penalised - plain: full step {(pfull - full)*1e6:+8.1f} us, "
               f"graph GPU {(preplay - replay)*1e6:+8.1f} us")
+    if "--topk" in sys.argv[1:]:
+        samp = dict(temperature=0.8, top_k=40, top_p=0.9)
+        eng._GRAPH_TOPK = eng._TOPK_HIP = False
+        hfull, _ = measure(eng, cfg, users, "class-3 host", **samp)
+        eng._GRAPH_TOPK = eng._TOPK_HIP = True
+        kfull, _ = measure(eng, cfg, users, "class-2 hip", klass=2, **samp)
+        print(f"top_k 40 / top_p 0.9 full step: class 3 {hfull*1e3:7.3f} ms, "
+              f"class 2 hip tail {kfull*1e3:7.3f} ms "
+              f"({(kfull - hfull)*1e6:+8.1f} us)")
 
 
 if __name__ == "__main__":
