@@ -15,11 +15,10 @@
 //
 // fragout: the attention OUTPUT is written in the fused-chain frag layout
 // (common.cuh frag_off) so the o-GEMM streams it linearly.
-#include "common.cuh"
-
-#define DCHUNK 64
-#define DHEAD 128
-#define DKPAD 4
+//
+// The segment sweep, the partial merge and the output store are defined
+// once in decode_attn.cuh; decode_attn_blk.hip is the second caller.
+#include "decode_attn.cuh"
 
 // grid: (n_seqs * split, KVH); block: G*64 threads (G templated: the
 // next-chunk register-prefetch array must be compile-time sized, guide
@@ -53,38 +52,16 @@ __global__ __launch_bounds__(GT * 64, 1) void k_decode_attn(
     const int lane = threadIdx.x & 63;
     const int qh = kvh * G + wid;
 
-    constexpr int NTHR = GT * 64;
-    constexpr int NSLOT = CH * (DHEAD / 8);       // uint4 slots per tile
-    constexpr int NPF = (NSLOT + NTHR - 1) / NTHR;  // prefetch regs/thread
-    // Register-prefetch pipeline for every GQA group a preset uses.
-    // Non-dividing groups (G=7, Qwen2: 1024 slots over 448 threads)
-    // clamp the tail slot exactly like the prefill stager — duplicate
-    // threads re-load/re-write identical bytes, which is benign, while a
-    // guarded load/write would de-pipeline the stage (traps (c)).
-    // NPF=8 (G=1 at chunk 32, G=2 at chunk 64) costs 64 VGPRs — free at
-    // the 1-2 wave/SIMD occupancy LDS already imposes there.
-    constexpr bool PF =
-        (NPF <= 8) && (NSLOT % NTHR == 0 || NPF == 3);
-
     const int slot = slot_ids[S_idx];
     const int kv_len = seq_lens[S_idx];
-    // balanced segment bounds in whole chunks (pages don't straddle
-    // chunks): ceil-div per_seg gave e.g. 9 chunks @ split 4 -> 3,3,3,0
-    // with a whole workgroup idle; floor-interpolated bounds give 2,2,2,3
-    const int n_chunks = (kv_len + CH - 1) / CH;
-    // sliding window: the (single) query sits at kv_len-1, so only keys
-    // >= lo_tok participate; split the ACTIVE chunk range
-    const int lo_tok = (window > 0 && kv_len > window) ? kv_len - window : 0;
-    const int ch_base = lo_tok / CH;
-    const int n_act = n_chunks - ch_base;
-    const int c0 = ch_base + (int)(((int64_t)n_act * seg) / split);
-    const int c1 = ch_base + (int)(((int64_t)n_act * (seg + 1)) / split);
+    const DecodeRange rg = decode_range(kv_len, window, CH);
+    const int c0 = decode_seg_bound(rg, seg, split);
+    const int c1 = decode_seg_bound(rg, seg + 1, split);
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int KROW = DHEAD + DKPAD;
     bf16* k_tile = reinterpret_cast<bf16*>(smem);
-    bf16* v_tile = k_tile + CH * KROW;
-    float* q_lds = reinterpret_cast<float*>(v_tile + CH * KROW); // [G][128]
+    bf16* v_tile = k_tile + CH * DKROW;
+    float* q_lds = reinterpret_cast<float*>(v_tile + CH * DKROW); // [G][128]
     // p row is per-LANE (65 = 64+pad), NOT per-chunk-key: every lane
     // stores its p (dead lanes 0.0), so a CH=32 row of 33 floats would
     // send lanes 32-63 past the row (OOB at G=1, cross-wave race at G>1)
@@ -99,165 +76,16 @@ __global__ __launch_bounds__(GT * 64, 1) void k_decode_attn(
     __syncthreads();
 
     float m = -3.0e38f, l = 0.f, o0 = 0.f, o1 = 0.f;
-
-    // clamp instead of guarding: a conditional load would de-pipeline the
-    // whole stage (guide §5 traps (c)); the duplicated tail rows are
-    // masked to p=0 by the softmax
-    auto src_of = [&](int base, int u) -> int64_t {
-        const int tok = u / (DHEAD / 8), dv = u % (DHEAD / 8);
-        const int tk = base + tok < kv_len ? base + tok : kv_len - 1;
-        return paged_kv_row(page_table, slot, max_pages, tk, page, KVH, kvh)
-               + dv * 8;
-    };
-    auto stage_direct = [&](int ch2) {
-        const int base2 = ch2 * CH;
-        for (int u = threadIdx.x; u < NSLOT; u += NTHR) {
-            const int tok = u / (DHEAD / 8), dv = u % (DHEAD / 8);
-            const int64_t src = src_of(base2, u);
-            *reinterpret_cast<uint4*>(k_tile + tok * KROW + dv * 8) =
-                *reinterpret_cast<const uint4*>(kpool + src);
-            *reinterpret_cast<uint4*>(v_tile + tok * KROW + dv * 8) =
-                *reinterpret_cast<const uint4*>(vpool + src);
-        }
-    };
-
-    if (c0 < c1) stage_direct(c0);
-    __syncthreads();
-
-    for (int ch = c0; ch < c1; ch++) {
-        const int base = ch * CH;
-        const int n_here = min(CH, kv_len - base);
-        // ---- issue next chunk's HBM loads NOW, write to LDS after the
-        // compute phase (T14 issue-early/write-late): the fetch rides
-        // under the score/PV work instead of serializing with it.
-        // Named registers, not an array — hipcc demotes even
-        // constant-indexed uint4 arrays here to scratch (24 scratch ops,
-        // 144 B/lane), and a spilled prefetch is HBM traffic, not a win.
-        uint4 k0, k1, k2, k3, v0, v1, v2, v3;
-        uint4 k4, k5, k6, k7, v4, v5, v6, v7;
-        const bool have_next = PF && (ch + 1 < c1);
-        if (have_next) {
-            const int nbase = (ch + 1) * CH;
-            const int64_t s0 = src_of(nbase, threadIdx.x);
-            const int64_t s1 = NPF >= 2 ? src_of(nbase, threadIdx.x + NTHR)
-                                        : s0;
-            k0 = *reinterpret_cast<const uint4*>(kpool + s0);
-            v0 = *reinterpret_cast<const uint4*>(vpool + s0);
-            if constexpr (NPF >= 2) {
-                k1 = *reinterpret_cast<const uint4*>(kpool + s1);
-                v1 = *reinterpret_cast<const uint4*>(vpool + s1);
-            }
-            if constexpr (NPF >= 3) {
-                const int64_t s2 = src_of(
-                    nbase, min((int)threadIdx.x + 2 * NTHR, NSLOT - 1));
-                k2 = *reinterpret_cast<const uint4*>(kpool + s2);
-                v2 = *reinterpret_cast<const uint4*>(vpool + s2);
-            }
-            if constexpr (NPF >= 4) {
-                const int64_t s3 = src_of(nbase, threadIdx.x + 3 * NTHR);
-                k3 = *reinterpret_cast<const uint4*>(kpool + s3);
-                v3 = *reinterpret_cast<const uint4*>(vpool + s3);
-            }
-            if constexpr (NPF >= 8) {
-                const int64_t s4 = src_of(nbase, threadIdx.x + 4 * NTHR);
-                const int64_t s5 = src_of(nbase, threadIdx.x + 5 * NTHR);
-                const int64_t s6 = src_of(nbase, threadIdx.x + 6 * NTHR);
-                const int64_t s7 = src_of(nbase, threadIdx.x + 7 * NTHR);
-                k4 = *reinterpret_cast<const uint4*>(kpool + s4);
-                v4 = *reinterpret_cast<const uint4*>(vpool + s4);
-                k5 = *reinterpret_cast<const uint4*>(kpool + s5);
-                v5 = *reinterpret_cast<const uint4*>(vpool + s5);
-                k6 = *reinterpret_cast<const uint4*>(kpool + s6);
-                v6 = *reinterpret_cast<const uint4*>(vpool + s6);
-                k7 = *reinterpret_cast<const uint4*>(kpool + s7);
-                v7 = *reinterpret_cast<const uint4*>(vpool + s7);
-            }
-        }
-
-        // ---- score for key j = lane ----
-        float s = 0.f;
-        const bool live = lane < n_here && base + lane >= lo_tok;
-        {
-            const bf16* krow = k_tile + lane * KROW;
-            const float* qrow = q_lds + wid * DHEAD;
-            #pragma unroll
-            for (int d = 0; d < DHEAD; d += 8) {
-                float k8[8];
-                load8f(krow + d, k8);
-                s += k8[0] * qrow[d] + k8[1] * qrow[d + 1]
-                   + k8[2] * qrow[d + 2] + k8[3] * qrow[d + 3]
-                   + k8[4] * qrow[d + 4] + k8[5] * qrow[d + 5]
-                   + k8[6] * qrow[d + 6] + k8[7] * qrow[d + 7];
-            }
-            s = live ? s * scale : -3.0e38f;
-        }
-
-        // ---- online softmax ----
-        const float smax = wave_reduce_max(s);
-        float p = 0.f;
-        if (smax > -3.0e38f) {
-            const float mn = fmaxf(m, smax);
-            const float corr = __expf(m - mn);
-            p = live ? __expf(s - mn) : 0.f;
-            l = l * corr + wave_reduce_sum(p);
-            o0 *= corr; o1 *= corr;
-            m = mn;
-        }
-        p_lds[wid * 65 + lane] = p;
-
-        // ---- PV: lane accumulates dims (2*lane, 2*lane+1) ----
-        // fixed bound + full unroll: a runtime bound left this loop a
-        // serial ds_read latency chain (PMC: 25% SQ_WAIT_INST_ANY);
-        // dead keys contribute p=0 so looping to CH is exact
-        const float* prow = p_lds + wid * 65;
-        #pragma unroll 8
-        for (int j = 0; j < CH; j++) {
-            const bf162 v2 = *reinterpret_cast<const bf162*>(
-                v_tile + j * KROW + 2 * lane);
-            const float pj = prow[j];
-            o0 = fmaf(pj, bf2f(v2.x), o0);
-            o1 = fmaf(pj, bf2f(v2.y), o1);
-        }
-        __syncthreads();  // every wave done reading the k/v tiles
-        if (have_next) {
-            auto put = [&](int u, uint4 kx, uint4 vx) {
-                const int tok = u / (DHEAD / 8), dv = u % (DHEAD / 8);
-                *reinterpret_cast<uint4*>(k_tile + tok * KROW + dv * 8)
-                    = kx;
-                *reinterpret_cast<uint4*>(v_tile + tok * KROW + dv * 8)
-                    = vx;
-            };
-            put(threadIdx.x, k0, v0);
-            if constexpr (NPF >= 2) put(threadIdx.x + NTHR, k1, v1);
-            if constexpr (NPF >= 3)
-                put(min((int)threadIdx.x + 2 * NTHR, NSLOT - 1), k2, v2);
-            if constexpr (NPF >= 4) put(threadIdx.x + 3 * NTHR, k3, v3);
-            if constexpr (NPF >= 8) {
-                put(threadIdx.x + 4 * NTHR, k4, v4);
-                put(threadIdx.x + 5 * NTHR, k5, v5);
-                put(threadIdx.x + 6 * NTHR, k6, v6);
-                put(threadIdx.x + 7 * NTHR, k7, v7);
-            }
-            __syncthreads();  // tiles ready for next iteration
-        } else if (!PF && ch + 1 < c1) {
-            stage_direct(ch + 1);
-            __syncthreads();
-        }
-    }
+    decode_attn_segment<GT, CH, false>(
+        k_tile, v_tile, q_lds + wid * DHEAD, p_lds + wid * 65, kpool, vpool,
+        page_table, slot, kv_len, rg.lo_tok, kvh, KVH, page, max_pages,
+        scale, threadIdx.x, lane, c0, c1, 0, m, l, o0, o1);
 
     // ---- emit ----
     if (split == 1) {
         const float linv = l > 0.f ? 1.f / l : 0.f;
-        const bf162 ov =
-            __float22bfloat162_rn(make_float2(o0 * linv, o1 * linv));
-        if (fragout)
-            *reinterpret_cast<bf162*>(
-                out + (int64_t)(S_idx >> 5) * 32 * Hq * DHEAD
-                    + frag_off(S_idx & 31, qh * DHEAD + 2 * lane))
-                = ov;
-        else
-            reinterpret_cast<bf162*>(
-                out + ((int64_t)S_idx * Hq + qh) * DHEAD)[lane] = ov;
+        decode_store(out, S_idx, qh, Hq, lane, fragout, o0 * linv,
+                     o1 * linv);
         return;
     }
     {
@@ -295,35 +123,11 @@ __global__ __launch_bounds__(GT * 64, 1) void k_decode_attn(
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();              // acquire visible to the whole block
-    {
-        // wave `wid` reduces its head, lane covers dims (2*lane, 2*lane+1)
-        const int64_t sh = (int64_t)S_idx * Hq + qh;
-        float mm = -3.0e38f;
-        for (int i = 0; i < split; i++)
-            mm = fmaxf(mm, ml_part[(sh * split + i) * 2]);
-        float ll = 0.f, a0 = 0.f, a1 = 0.f;
-        for (int i = 0; i < split; i++) {
-            const int64_t pi = sh * split + i;
-            const float mi = ml_part[pi * 2];
-            if (mi <= -3.0e38f) continue;
-            const float w = __expf(mi - mm);
-            ll += w * ml_part[pi * 2 + 1];
-            const float* op = o_part + pi * DHEAD;
-            a0 = fmaf(w, op[2 * lane], a0);
-            a1 = fmaf(w, op[2 * lane + 1], a1);
-        }
-        const float linv = ll > 0.f ? 1.f / ll : 0.f;
-        if (fragout) {
-            *reinterpret_cast<bf162*>(
-                out + (int64_t)(S_idx >> 5) * 32 * Hq * DHEAD
-                    + frag_off(S_idx & 31, qh * DHEAD + 2 * lane)) =
-                __float22bfloat162_rn(
-                    make_float2(a0 * linv, a1 * linv));
-            return;
-        }
-        reinterpret_cast<bf162*>(out + sh * DHEAD)[lane] =
-            __float22bfloat162_rn(make_float2(a0 * linv, a1 * linv));
-    }
+    // wave `wid` reduces its head, lane covers dims (2*lane, 2*lane+1)
+    const int64_t sh = (int64_t)S_idx * Hq + qh;
+    decode_merge_store(out, o_part + sh * split * DHEAD,
+                       ml_part + sh * split * 2, split, S_idx, qh, Hq, lane,
+                       fragout);
 }
 
 // combine: one wave per (seq, head); merges the split online-softmax
@@ -336,30 +140,9 @@ __global__ __launch_bounds__(256) void k_decode_combine(
     const int sh = blockIdx.x * 4 + (threadIdx.x >> 6);  // seq*Hq + head
     const int lane = threadIdx.x & 63;
     if (sh >= total) return;
-    float m = -3.0e38f;
-    for (int i = 0; i < split; i++)
-        m = fmaxf(m, ml_part[((int64_t)sh * split + i) * 2]);
-    float l = 0.f, a0 = 0.f, a1 = 0.f;
-    for (int i = 0; i < split; i++) {
-        const int64_t pi = (int64_t)sh * split + i;
-        const float mi = ml_part[pi * 2];
-        if (mi <= -3.0e38f) continue;
-        const float w = __expf(mi - m);
-        l += w * ml_part[pi * 2 + 1];
-        const float* op = o_part + pi * DHEAD;
-        a0 = fmaf(w, op[2 * lane], a0);
-        a1 = fmaf(w, op[2 * lane + 1], a1);
-    }
-    const float linv = l > 0.f ? 1.f / l : 0.f;
-    const bf162 ov =
-        __float22bfloat162_rn(make_float2(a0 * linv, a1 * linv));
-    if (fragout)
-        *reinterpret_cast<bf162*>(
-            out + (int64_t)((sh / Hq) >> 5) * 32 * Hq * DHEAD
-                + frag_off((sh / Hq) & 31,
-                           (sh % Hq) * DHEAD + 2 * lane)) = ov;
-    else
-        reinterpret_cast<bf162*>(out + (int64_t)sh * DHEAD)[lane] = ov;
+    decode_merge_store(out, o_part + (int64_t)sh * split * DHEAD,
+                       ml_part + (int64_t)sh * split * 2, split, sh / Hq,
+                       sh % Hq, Hq, lane, fragout);
 }
 
 extern "C" int decode_attn_bf16(
@@ -370,8 +153,7 @@ extern "C" int decode_attn_bf16(
     int window, int chunk, void* sem, int fragout, hipStream_t stream)
 {
     const int G = Hq / KVH;
-    const int lds = 2 * chunk * (DHEAD + DKPAD) * 2 + G * DHEAD * 4
-                  + G * 65 * 4;
+    const int lds = decode_tile_bytes(chunk) + G * DHEAD * 4 + G * 65 * 4;
     dim3 grid(S * split, KVH);
 #define DA_LAUNCH1(GT, CH)                                                \
     k_decode_attn<GT, CH><<<grid, GT * 64, lds, stream>>>(                \

@@ -40,6 +40,9 @@ def _signatures():
         "argmax_bf16": [vp, vp, i, i, vp, vp, i, vp],
         "decode_attn_bf16": [vp, vp, vp, vp, vp, vp, vp, vp, vp,
                              i, i, i, i, i, f, i64, i, i, i, vp, i, vp],
+        "decode_attn_blk_prepare": [i, i, i],
+        "decode_attn_blk_bf16": [vp, vp, vp, vp, vp, vp, vp,
+                                 i, i, i, i, i, f, i64, i, i, i, i, vp],
         "rope_append_bf16": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                              i, i, i, i, i, i, i64, i64, i64, vp],
         "prefill_attn_bf16": [vp, vp, vp, vp, vp, vp, vp, vp, vp,
@@ -333,6 +336,52 @@ def _decode_chunk(G):
     return 32 if G == 1 else 64
 
 
+# k_decode_attn_blk<G, chunk, split> instantiations (decode_attn_blk.hip
+# BLK_INSTANCES): split in {2, 4} with split * G <= 16 waves, at the chunk
+# _decode_chunk picks by default
+_BLK_INSTANCES = frozenset(
+    (G, 32 if G == 1 else 64, split)
+    for split in (2, 4) for G in range(1, 9) if split * G <= 16)
+# below this many (sequence, kv-head) pairs the block path leaves CUs
+# empty and the finer one-block-per-segment grid places better
+_BLK_MIN_BLOCKS = 128
+
+
+def decode_blocksplit(S, KVH, G, chunk, split, env=None):
+    """True when attention_decode runs the split as ONE block per
+    (sequence, kv-head) that merges its segments through LDS
+    (k_decode_attn_blk) instead of one block per segment plus
+    k_decode_combine.  Pure: `env` stands in for os.environ.
+    OLLAMAMQ_DECODE_BLOCKSPLIT=0 forces the two-kernel path, =1 waives
+    only the S * KVH floor (A/B at small shapes)."""
+    env = os.environ if env is None else env
+    gate = env.get("OLLAMAMQ_DECODE_BLOCKSPLIT")
+    if gate == "0" or env.get("OLLAMAMQ_FUSED_COMBINE") == "1":
+        return False
+    if split <= 1 or (G, chunk, split) not in _BLK_INSTANCES:
+        return False
+    return gate == "1" or S * KVH >= _BLK_MIN_BLOCKS
+
+
+_blk_ready = {}
+
+
+def _blk_prepare(G, chunk, split):
+    """Opt one instantiation in to its dynamic LDS size (above 64 KB at
+    G = 4, split 4), once.  False when the runtime refuses it: the caller
+    keeps the two-kernel path."""
+    key = (G, chunk, split)
+    ok = _blk_ready.get(key)
+    if ok is None:
+        err = _lib.decode_attn_blk_prepare(G, chunk, split)
+        ok = _blk_ready[key] = err == 0
+        if not ok:
+            import warnings
+            warnings.warn(f"decode block-split {key}: LDS opt-in refused "
+                          f"(hipError {err}); keeping the two-kernel path")
+    return ok
+
+
 def attention_decode(q, cache, layer, meta, fragout=False):
     """Flash-decoding: KV-split partials + exact online-softmax combine.
 
@@ -340,7 +389,10 @@ def attention_decode(q, cache, layer, meta, fragout=False):
     fills the 256-CU chip (a bare (seq, kv-head) grid at batch 32 is 1
     workgroup/CU and runs at ~10% of HBM bandwidth).
     fragout: emit the output in the fused-chain 32-row frag layout (the
-    o GEMM streams it linearly like packed weights)."""
+    o GEMM streams it linearly like packed weights).
+    Where decode_blocksplit() says so, the split's segments share one
+    block per (sequence, kv-head) and merge in LDS (k_decode_attn_blk):
+    same arithmetic, bit-identical output, no partials, one launch."""
     S, Hq, D = q.shape
     assert D == 128
     out = torch.empty((((S + 31) // 32) * 32 * Hq * D,)
@@ -357,6 +409,18 @@ def attention_decode(q, cache, layer, meta, fragout=False):
         want = int(env)
     max_seg = max(1, (meta.max_kv + 63) // 64)
     split = int(min(want, max_seg, 32))
+    G, chunk = Hq // kvh, _decode_chunk(Hq // kvh)
+    slot32, len32 = _i32(meta.slot_ids), _i32(meta.seq_lens)
+    if decode_blocksplit(S, kvh, G, chunk, split) \
+            and _blk_prepare(G, chunk, split):
+        # one block per (sequence, kv-head); no partial scratch
+        _check(_lib.decode_attn_blk_bf16(
+            _p(out), _p(q), kp, vp, _p(cache.page_table),
+            _p(slot32), _p(len32), S, Hq, kvh, cache.page_size,
+            cache.page_table.shape[1], 1.0 / (D ** 0.5), _row_stride(q, D),
+            split, meta.window, chunk, 1 if fragout else 0, _stream()),
+            "decode_attn_blk")
+        return out
     o_part, ml_part = (None, None)
     op = mp = ctypes.c_void_p(0)
     sem = ctypes.c_void_p(0)
@@ -370,12 +434,11 @@ def attention_decode(q, cache, layer, meta, fragout=False):
         # fewer, longer blocks.
         if os.environ.get("OLLAMAMQ_FUSED_COMBINE") == "1":
             sem = _p(_combine_sem(S, kvh, q.device))
-    slot32, len32 = _i32(meta.slot_ids), _i32(meta.seq_lens)
     _check(_lib.decode_attn_bf16(
         _p(out), op, mp, _p(q), kp, vp, _p(cache.page_table),
         _p(slot32), _p(len32), S, Hq, kvh, cache.page_size,
         cache.page_table.shape[1], 1.0 / (D ** 0.5), _row_stride(q, D),
-        split, meta.window, _decode_chunk(Hq // kvh), sem,
+        split, meta.window, chunk, sem,
         1 if fragout else 0, _stream()),
         "decode_attn")
     return out

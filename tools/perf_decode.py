@@ -1,4 +1,5 @@
-"""Microbench: decode attention old (unsplit) vs flash-decoding path.
+"""Microbench: decode attention old (unsplit) vs flash-decoding path
+(two-kernel split and block-split).
 
 Run on a GPU box:  python tools/perf_decode.py [ctx] [batch]
 """
@@ -58,8 +59,20 @@ def main():
         print(f"{label}: {dt*1e6:8.1f} us  {kv_bytes/dt/1e12:6.2f} TB/s")
         return out
 
-    o_new = bench(lambda l: hip.attention_decode(q, cache, l, meta),
-                  "split ")
+    def path(blk):
+        os.environ["OLLAMAMQ_DECODE_BLOCKSPLIT"] = "1" if blk else "0"
+        return lambda l: hip.attention_decode(q, cache, l, meta)
+
+    o_new = bench(path(False), "split ")
+    G = Hq // KVH
+    split = min(max(1, 1024 // (B * KVH)), (ctx + 63) // 64, 32)
+    if hip.decode_blocksplit(B, KVH, G, hip._decode_chunk(G), split,
+                             {"OLLAMAMQ_DECODE_BLOCKSPLIT": "1"}):
+        o_blk = bench(path(True), "block ")
+        assert torch.equal(o_blk, o_new), "block path differs from split"
+    else:
+        print(f"block : not instantiated for G={G} split={split}")
+    os.environ["OLLAMAMQ_DECODE_BLOCKSPLIT"] = "0"
     for sp in (1, 2, 4, 8):
         bench(lambda l, sp=sp: hip.decode_pure(cache, l, meta, sp),
               f"pure{sp}")
