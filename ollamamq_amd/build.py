@@ -57,7 +57,8 @@ def build_kernels(force=False):
 # no packed fp32 arithmetic (v_pk_*_f32) in kernels written from here on
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 _KERNEL_FLAGS = {"topk_sample.hip": _NO_PK_F32,
-                 "decode_attn_blk.hip": _NO_PK_F32}
+                 "decode_attn_blk.hip": _NO_PK_F32,
+                 "prefill_attn_kv8.hip": _NO_PK_F32}
 
 
 def build_dispatcher(force=False):

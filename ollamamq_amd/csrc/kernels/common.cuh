@@ -127,6 +127,65 @@ DEV int64_t paged_kv_row(const int* page_table, int slot, int max_pages,
 }
 
 // ---------------------------------------------------------------------------
+// KV pool storage formats.  KVF 0: bf16 elements (the layout above).  KVF 1:
+// OCP e4m3fn codes at unit scale, one byte per element, same [P][KVH][page]
+// [128] shape, so paged_kv_row's element offset is the byte offset.  A
+// reader moves an 8-dim piece as `vec8` (16 or 8 bytes) and widens it to 8
+// bf16 on the way into LDS; every e4m3 value is exact in bf16, so all code
+// after staging sees the numbers a bf16 pool of the decoded values holds.
+// ---------------------------------------------------------------------------
+template <int KVF> struct KvFmt;
+template <> struct KvFmt<0> {
+    typedef bf16 elem;
+    typedef uint4 vec8;
+    static __device__ __forceinline__ uint4 widen(uint4 v) { return v; }
+};
+template <> struct KvFmt<1> {
+    typedef uint8_t elem;
+    typedef uint2 vec8;
+    static __device__ __forceinline__ uint4 widen(uint2 c) {
+        union { bf16x8 v; uint4 u; } o;
+        o.v = fp8x8_to_bf16x8(c.x, c.y);
+        return o.u;
+    }
+};
+
+// The KV store rule: bf16 bits -> e4m3fn code of clamp(x, +-448) rounded to
+// nearest, ties to even (ops/quant.py kv_fp8_encode is the same rule).
+// Integer arithmetic only: a bf16 is sign, 8-bit exponent, 7-bit mantissa;
+// a normal e4m3 keeps 3 mantissa bits, so rounding drops 4 bits and the
+// carry runs into the exponent field by itself; below 2^-6 the grid is
+// uniform, 2^-9.  +-inf and everything >= 448 store +-448, a NaN stores
+// 0x7f with its sign, -0.0 keeps its sign.
+DEV unsigned bf16_to_e4m3(unsigned b) {
+    const unsigned sign = (b >> 8) & 0x80u, a = b & 0x7fffu;
+    if (a > 0x7f80u) return sign | 0x7fu;          // NaN
+    if (a >= 0x43e0u) return sign | 0x7eu;         // >= 448, inf
+    const int E = (int)(a >> 7);                   // biased by 127
+    if (E >= 121)                                  // >= 2^-6: normal code
+        return sign | (((a + 7u + ((a >> 4) & 1u)) >> 4) - (120u << 3));
+    if (E < 117) return sign;                      // < 2^-10: rounds to 0
+    const unsigned mant = (a & 0x7fu) | 0x80u;     // value = mant * 2^(E-134)
+    const int sh = 125 - E;                        // code = mant / 2^sh, 5..8
+    unsigned q = mant >> sh;
+    const unsigned rem = mant & ((1u << sh) - 1u), half = 1u << (sh - 1);
+    q += (rem > half || (rem == half && (q & 1u))) ? 1u : 0u;
+    return sign | q;                               // 8 is code 0x08 = 2^-6
+}
+
+// two bf16 (one dword, low element first) -> two codes in the low 16 bits
+DEV unsigned bf16x2_to_e4m3x2(unsigned w) {
+    return bf16_to_e4m3(w & 0xffffu) | (bf16_to_e4m3(w >> 16) << 8);
+}
+
+// 8 bf16 (16 bytes) -> 8 codes (8 bytes), ascending
+DEV uint2 bf16x8_to_e4m3x8(uint4 v) {
+    return make_uint2(
+        bf16x2_to_e4m3x2(v.x) | (bf16x2_to_e4m3x2(v.y) << 16),
+        bf16x2_to_e4m3x2(v.z) | (bf16x2_to_e4m3x2(v.w) << 16));
+}
+
+// ---------------------------------------------------------------------------
 // Counter-based sampler noise, shared by the Gumbel sampler (kernels.hip)
 // and the top-k/top-p sampler (topk_sample.hip).
 // ---------------------------------------------------------------------------

@@ -46,15 +46,24 @@ DEV int decode_seg_bound(const DecodeRange& r, int seg, int split) {
 // every one of them runs `n_rounds` (block-uniform, >= c1 - c0) rounds; a
 // segment with no chunk left in a round issues no loads and does no
 // arithmetic but still reaches both barriers.
-template <int GT, int CH, bool MULTI>
+//
+// KVF is the pool's storage format (common.cuh KvFmt).  With e4m3 pools
+// the prefetch registers hold codes, 8 bytes per 8-dim piece, and are
+// widened to bf16 once per block on the way into the same padded tiles
+// (put / stage_direct), shared by the GT waves; from the tiles on nothing
+// differs, so the output is bit-equal to a bf16 pool of the decoded values.
+template <int GT, int CH, bool MULTI, int KVF = 0>
 DEV void decode_attn_segment(
     bf16* k_tile, bf16* v_tile, const float* qrow, float* prow,
-    const bf16* __restrict__ kpool, const bf16* __restrict__ vpool,
+    const typename KvFmt<KVF>::elem* __restrict__ kpool,
+    const typename KvFmt<KVF>::elem* __restrict__ vpool,
     const int* __restrict__ page_table, int slot, int kv_len, int lo_tok,
     int kvh, int KVH, int page, int max_pages, float scale,
     int tid, int lane, int c0, int c1, int n_rounds,
     float& m, float& l, float& o0, float& o1)
 {
+    typedef KvFmt<KVF> F;
+    typedef typename F::vec8 vec8;        // one 8-dim piece as stored
     constexpr int NTHR = GT * 64;
     constexpr int KROW = DKROW;
     constexpr int NSLOT = CH * (DHEAD / 8);       // uint4 slots per tile
@@ -83,10 +92,17 @@ DEV void decode_attn_segment(
         for (int u = tid; u < NSLOT; u += NTHR) {
             const int tok = u / (DHEAD / 8), dv = u % (DHEAD / 8);
             const int64_t src = src_of(base2, u);
-            *reinterpret_cast<uint4*>(k_tile + tok * KROW + dv * 8) =
-                *reinterpret_cast<const uint4*>(kpool + src);
-            *reinterpret_cast<uint4*>(v_tile + tok * KROW + dv * 8) =
-                *reinterpret_cast<const uint4*>(vpool + src);
+            if constexpr (KVF == 0) {     // plain 16-byte copies
+                *reinterpret_cast<uint4*>(k_tile + tok * KROW + dv * 8) =
+                    *reinterpret_cast<const uint4*>(kpool + src);
+                *reinterpret_cast<uint4*>(v_tile + tok * KROW + dv * 8) =
+                    *reinterpret_cast<const uint4*>(vpool + src);
+            } else {
+                *reinterpret_cast<uint4*>(k_tile + tok * KROW + dv * 8) =
+                    F::widen(*reinterpret_cast<const vec8*>(kpool + src));
+                *reinterpret_cast<uint4*>(v_tile + tok * KROW + dv * 8) =
+                    F::widen(*reinterpret_cast<const vec8*>(vpool + src));
+            }
         }
     };
 
@@ -106,43 +122,43 @@ DEV void decode_attn_segment(
         // Named registers, not an array — hipcc demotes even
         // constant-indexed uint4 arrays here to scratch (24 scratch ops,
         // 144 B/lane), and a spilled prefetch is HBM traffic, not a win.
-        uint4 k0, k1, k2, k3, v0, v1, v2, v3;
-        uint4 k4, k5, k6, k7, v4, v5, v6, v7;
+        vec8 k0, k1, k2, k3, v0, v1, v2, v3;
+        vec8 k4, k5, k6, k7, v4, v5, v6, v7;
         const bool have_next = PF && (ch + 1 < c1);
         if (have_next) {
             const int nbase = (ch + 1) * CH;
             const int64_t s0 = src_of(nbase, tid);
             const int64_t s1 = NPF >= 2 ? src_of(nbase, tid + NTHR) : s0;
-            k0 = *reinterpret_cast<const uint4*>(kpool + s0);
-            v0 = *reinterpret_cast<const uint4*>(vpool + s0);
+            k0 = *reinterpret_cast<const vec8*>(kpool + s0);
+            v0 = *reinterpret_cast<const vec8*>(vpool + s0);
             if constexpr (NPF >= 2) {
-                k1 = *reinterpret_cast<const uint4*>(kpool + s1);
-                v1 = *reinterpret_cast<const uint4*>(vpool + s1);
+                k1 = *reinterpret_cast<const vec8*>(kpool + s1);
+                v1 = *reinterpret_cast<const vec8*>(vpool + s1);
             }
             if constexpr (NPF >= 3) {
                 const int64_t s2 = src_of(
                     nbase, min(tid + 2 * NTHR, NSLOT - 1));
-                k2 = *reinterpret_cast<const uint4*>(kpool + s2);
-                v2 = *reinterpret_cast<const uint4*>(vpool + s2);
+                k2 = *reinterpret_cast<const vec8*>(kpool + s2);
+                v2 = *reinterpret_cast<const vec8*>(vpool + s2);
             }
             if constexpr (NPF >= 4) {
                 const int64_t s3 = src_of(nbase, tid + 3 * NTHR);
-                k3 = *reinterpret_cast<const uint4*>(kpool + s3);
-                v3 = *reinterpret_cast<const uint4*>(vpool + s3);
+                k3 = *reinterpret_cast<const vec8*>(kpool + s3);
+                v3 = *reinterpret_cast<const vec8*>(vpool + s3);
             }
             if constexpr (NPF >= 8) {
                 const int64_t s4 = src_of(nbase, tid + 4 * NTHR);
                 const int64_t s5 = src_of(nbase, tid + 5 * NTHR);
                 const int64_t s6 = src_of(nbase, tid + 6 * NTHR);
                 const int64_t s7 = src_of(nbase, tid + 7 * NTHR);
-                k4 = *reinterpret_cast<const uint4*>(kpool + s4);
-                v4 = *reinterpret_cast<const uint4*>(vpool + s4);
-                k5 = *reinterpret_cast<const uint4*>(kpool + s5);
-                v5 = *reinterpret_cast<const uint4*>(vpool + s5);
-                k6 = *reinterpret_cast<const uint4*>(kpool + s6);
-                v6 = *reinterpret_cast<const uint4*>(vpool + s6);
-                k7 = *reinterpret_cast<const uint4*>(kpool + s7);
-                v7 = *reinterpret_cast<const uint4*>(vpool + s7);
+                k4 = *reinterpret_cast<const vec8*>(kpool + s4);
+                v4 = *reinterpret_cast<const vec8*>(vpool + s4);
+                k5 = *reinterpret_cast<const vec8*>(kpool + s5);
+                v5 = *reinterpret_cast<const vec8*>(vpool + s5);
+                k6 = *reinterpret_cast<const vec8*>(kpool + s6);
+                v6 = *reinterpret_cast<const vec8*>(vpool + s6);
+                k7 = *reinterpret_cast<const vec8*>(kpool + s7);
+                v7 = *reinterpret_cast<const vec8*>(vpool + s7);
             }
         }
 
@@ -193,12 +209,12 @@ DEV void decode_attn_segment(
         __syncthreads();  // every wave done reading the k/v tiles
         if (!more) continue;
         if (have_next) {
-            auto put = [&](int u, uint4 kx, uint4 vx) {
+            auto put = [&](int u, vec8 kx, vec8 vx) {
                 const int tok = u / (DHEAD / 8), dv = u % (DHEAD / 8);
                 *reinterpret_cast<uint4*>(k_tile + tok * KROW + dv * 8)
-                    = kx;
+                    = F::widen(kx);
                 *reinterpret_cast<uint4*>(v_tile + tok * KROW + dv * 8)
-                    = vx;
+                    = F::widen(vx);
             };
             put(tid, k0, v0);
             if constexpr (NPF >= 2) put(tid + NTHR, k1, v1);
@@ -253,4 +269,182 @@ DEV void decode_merge_store(bf16* __restrict__ out, const float* op,
     }
     const float linv = l > 0.f ? 1.f / l : 0.f;
     decode_store(out, S_idx, qh, Hq, lane, fragout, a0 * linv, a1 * linv);
+}
+
+// grid: (n_seqs * split, KVH); block: G*64 threads (G templated: the
+// next-chunk register-prefetch array must be compile-time sized, guide
+// rule 20 — runtime-indexed arrays land in scratch).
+// Partials: o_part [S][Hq][split][128] f32, ml_part [S][Hq][split][2] f32.
+// When split == 1, writes normalized bf16 straight to out.
+// launch_bounds min-waves/EU = 1: LDS (~37 KB/block) already caps
+// residency at 4 blocks/CU, so a high compiler occupancy target only
+// forces the prefetch registers to spill (measured 144 B/lane scratch)
+// KVF: pool storage format (common.cuh KvFmt).  The in-launch combine
+// (sem) exists for bf16 pools only.
+template <int GT, int CH, int KVF = 0>
+__global__ __launch_bounds__(GT * 64, 1) void k_decode_attn(
+    bf16* __restrict__ out,               // [S, Hq, D] (split==1)
+    float* __restrict__ o_part,           // split>1 partials
+    float* __restrict__ ml_part,
+    const bf16* __restrict__ q,           // [S, Hq, D] (row stride qs)
+    const typename KvFmt<KVF>::elem* __restrict__ kpool, // [P][KVH][page][D]
+    const typename KvFmt<KVF>::elem* __restrict__ vpool,
+    const int* __restrict__ page_table,   // [slots][max_pages]
+    const int* __restrict__ slot_ids,     // [S]
+    const int* __restrict__ seq_lens,     // [S] (kv length incl. this tok)
+    int Hq, int KVH, int page, int max_pages, float scale,
+    int64_t qs, int split, int window,    // window 0 = full causal
+    unsigned* __restrict__ sem,           // [S*KVH] tickets (fused combine)
+    int fragout)                          // out in fused-chain frag layout
+{
+    const int S_idx = blockIdx.x / split;
+    const int seg = blockIdx.x % split;
+    const int kvh = blockIdx.y;
+    constexpr int G = GT;
+    const int wid = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63;
+    const int qh = kvh * G + wid;
+
+    const int slot = slot_ids[S_idx];
+    const int kv_len = seq_lens[S_idx];
+    const DecodeRange rg = decode_range(kv_len, window, CH);
+    const int c0 = decode_seg_bound(rg, seg, split);
+    const int c1 = decode_seg_bound(rg, seg + 1, split);
+
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    bf16* k_tile = reinterpret_cast<bf16*>(smem);
+    bf16* v_tile = k_tile + CH * DKROW;
+    float* q_lds = reinterpret_cast<float*>(v_tile + CH * DKROW); // [G][128]
+    // p row is per-LANE (65 = 64+pad), NOT per-chunk-key: every lane
+    // stores its p (dead lanes 0.0), so a CH=32 row of 33 floats would
+    // send lanes 32-63 past the row (OOB at G=1, cross-wave race at G>1)
+    float* p_lds = q_lds + (int64_t)G * DHEAD;                       // [G][65]
+
+    // stage q (fp32 in LDS: repeated broadcast reads in the score loop)
+    if (wid < G) {
+        const bf16* qsrc = q + (int64_t)S_idx * qs + (int64_t)qh * DHEAD;
+        q_lds[wid * DHEAD + lane] = bf2f(qsrc[lane]);
+        q_lds[wid * DHEAD + lane + 64] = bf2f(qsrc[lane + 64]);
+    }
+    __syncthreads();
+
+    float m = -3.0e38f, l = 0.f, o0 = 0.f, o1 = 0.f;
+    decode_attn_segment<GT, CH, false, KVF>(
+        k_tile, v_tile, q_lds + wid * DHEAD, p_lds + wid * 65, kpool, vpool,
+        page_table, slot, kv_len, rg.lo_tok, kvh, KVH, page, max_pages,
+        scale, threadIdx.x, lane, c0, c1, 0, m, l, o0, o1);
+
+    // ---- emit ----
+    if (split == 1) {
+        const float linv = l > 0.f ? 1.f / l : 0.f;
+        decode_store(out, S_idx, qh, Hq, lane, fragout, o0 * linv,
+                     o1 * linv);
+        return;
+    }
+    {
+        const int64_t pi = (((int64_t)S_idx * Hq + qh) * split + seg);
+        float* op = o_part + pi * DHEAD;
+        op[2 * lane] = o0;
+        op[2 * lane + 1] = o1;
+        ml_part[pi * 2] = m;
+        ml_part[pi * 2 + 1] = l;
+    }
+    // separate k_decode_combine pass (the default; e4m3 pools always)
+    if (KVF != 0 || sem == nullptr) return;
+
+    // ---- in-launch combine (guide §6 G16 split-K recipe): publish the
+    // partials with an agent-scope release BEFORE the ticket fetch_add;
+    // the block that draws split-1 acquires and reduces its (seq, kvh)
+    // group — saves the combine kernel's launch boundary + HBM round trip
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();              // all waves' partials issued
+    int* flag = reinterpret_cast<int*>(smem);   // tiles are dead; reuse
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        // restate the post-wbl2 wait the compiler may drop (pitfall 12)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned t = __hip_atomic_fetch_add(
+            &sem[(int64_t)S_idx * gridDim.y + kvh], 1u,
+            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *flag = (t == (unsigned)(split - 1)) ? 1 : 0;
+    }
+    __syncthreads();
+    if (*flag == 0) return;
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        // reset for the next launch (stream-ordered; all arrivals done)
+        __hip_atomic_store(&sem[(int64_t)S_idx * gridDim.y + kvh], 0u,
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();              // acquire visible to the whole block
+    // wave `wid` reduces its head, lane covers dims (2*lane, 2*lane+1)
+    const int64_t sh = (int64_t)S_idx * Hq + qh;
+    decode_merge_store(out, o_part + sh * split * DHEAD,
+                       ml_part + sh * split * 2, split, S_idx, qh, Hq, lane,
+                       fragout);
+}
+
+// combine: one wave per (seq, head); merges the split online-softmax
+// partials exactly: m* = max m_i; o = Σ e^{m_i-m*} o_i; l = Σ e^{m_i-m*} l_i
+static __global__ __launch_bounds__(256) void k_decode_combine(
+    bf16* __restrict__ out, const float* __restrict__ o_part,
+    const float* __restrict__ ml_part, int total, int split,
+    int Hq, int fragout)
+{
+    const int sh = blockIdx.x * 4 + (threadIdx.x >> 6);  // seq*Hq + head
+    const int lane = threadIdx.x & 63;
+    if (sh >= total) return;
+    decode_merge_store(out, o_part + (int64_t)sh * split * DHEAD,
+                       ml_part + (int64_t)sh * split * 2, split, sh / Hq,
+                       sh % Hq, Hq, lane, fragout);
+}
+
+template <int KVF>
+static int decode_attn_launch(
+    void* out, void* o_part, void* ml_part, const void* q,
+    const void* kpool, const void* vpool, const void* page_table,
+    const void* slot_ids, const void* seq_lens, int S, int Hq, int KVH,
+    int page, int max_pages, float scale, int64_t q_stride, int split,
+    int window, int chunk, void* sem, int fragout, hipStream_t stream)
+{
+    typedef const typename KvFmt<KVF>::elem* pool_t;
+    if (KVF != 0 && sem != nullptr) return (int)hipErrorInvalidValue;
+    const int G = Hq / KVH;
+    const int lds = decode_tile_bytes(chunk) + G * DHEAD * 4 + G * 65 * 4;
+    dim3 grid(S * split, KVH);
+#define DA_LAUNCH1(GT, CH)                                                \
+    k_decode_attn<GT, CH, KVF><<<grid, GT * 64, lds, stream>>>(           \
+        (bf16*)out, (float*)o_part, (float*)ml_part, (const bf16*)q,      \
+        (pool_t)kpool, (pool_t)vpool, (const int*)page_table,             \
+        (const int*)slot_ids, (const int*)seq_lens, Hq, KVH, page,        \
+        max_pages, scale, q_stride, split, window, (unsigned*)sem,     \
+        fragout)
+// chunk is capped at 64: the score phase assigns ONE key per lane of a
+// wave64, so a larger staged chunk would silently drop keys 64+ (a 128
+// arm measured wrong before this guard)
+#define DA_LAUNCH(GT)                                                     \
+    switch (chunk) {                                                      \
+        case 32: DA_LAUNCH1(GT, 32); break;                               \
+        default: DA_LAUNCH1(GT, 64); break;                               \
+    }
+    switch (G) {
+        case 1: DA_LAUNCH(1); break;
+        case 2: DA_LAUNCH(2); break;
+        case 3: DA_LAUNCH(3); break;
+        case 4: DA_LAUNCH(4); break;
+        case 5: DA_LAUNCH(5); break;
+        case 6: DA_LAUNCH(6); break;
+        case 7: DA_LAUNCH(7); break;
+        case 8: DA_LAUNCH(8); break;
+        default: return (int)hipErrorInvalidValue;
+    }
+#undef DA_LAUNCH
+#undef DA_LAUNCH1
+    if (split > 1 && sem == nullptr) {
+        const int waves = S * Hq;
+        k_decode_combine<<<(waves + 3) / 4, 256, 0, stream>>>(
+            (bf16*)out, (const float*)o_part, (const float*)ml_part, waves,
+            split, Hq, fragout);
+    }
+    return (int)hipGetLastError();
 }

@@ -13,6 +13,10 @@
 // bit-identical to the two-kernel path.  No global partials, no fence, no
 // ticket, no second launch; q, slot_ids and seq_lens are read once per
 // (sequence, kv-head).
+//
+// This file also instantiates both decode kernels for e4m3 KV pools
+// (common.cuh KvFmt<1>): k_decode_attn_blk at every BLK_INSTANCES entry and
+// k_decode_attn (decode_attn.cuh) at every (G, chunk), entries *_kv8.
 #include "decode_attn.cuh"
 
 // dynamic LDS: q [GT][128] f32, then per segment K tile, V tile, p [GT][65]
@@ -26,12 +30,12 @@ constexpr int blk_lds_bytes(int GT, int CH, int NSEG) {
 // grid: (n_seqs, KVH); block: NSEG*GT*64 threads, wave w = segment w / GT,
 // head w % GT.  Barriers are block-wide, so every segment runs the longest
 // segment's round count and no wave returns before the last barrier.
-template <int GT, int CH, int NSEG>
+template <int GT, int CH, int NSEG, int KVF = 0>
 __global__ __launch_bounds__(NSEG * GT * 64, 1) void k_decode_attn_blk(
     bf16* __restrict__ out,               // [S, Hq, D] or frag layout
     const bf16* __restrict__ q,           // [S, Hq, D] (row stride qs)
-    const bf16* __restrict__ kpool,       // [P][KVH][page][D]
-    const bf16* __restrict__ vpool,
+    const typename KvFmt<KVF>::elem* __restrict__ kpool, // [P][KVH][page][D]
+    const typename KvFmt<KVF>::elem* __restrict__ vpool,
     const int* __restrict__ page_table,   // [slots][max_pages]
     const int* __restrict__ slot_ids,     // [S]
     const int* __restrict__ seq_lens,     // [S] (kv length incl. this tok)
@@ -72,7 +76,7 @@ __global__ __launch_bounds__(NSEG * GT * 64, 1) void k_decode_attn_blk(
     __syncthreads();
 
     float m = -3.0e38f, l = 0.f, o0 = 0.f, o1 = 0.f;
-    decode_attn_segment<GT, CH, true>(
+    decode_attn_segment<GT, CH, true, KVF>(
         k_tile, v_tile, q_lds + hw * DHEAD, p_lds + hw * 65, kpool, vpool,
         page_table, slot, kv_len, rg.lo_tok, kvh, KVH, page, max_pages,
         scale, (int)threadIdx.x - seg * GT * 64, lane, c0, c1, n_rounds,
@@ -112,17 +116,49 @@ __global__ __launch_bounds__(NSEG * GT * 64, 1) void k_decode_attn_blk(
 // (G, chunk, split) before its first launch.  Returns the runtime's error
 // when it refuses the size (the caller then keeps the two-kernel path), or
 // hipErrorInvalidValue for a combination that is not instantiated.
-extern "C" int decode_attn_blk_prepare(int G, int chunk, int split)
+template <int KVF>
+static int blk_prepare(int G, int chunk, int split)
 {
 #define BLK_PREPARE(GT, CH, NSEG)                                         \
     if (G == GT && chunk == CH && split == NSEG)                          \
         return (int)hipFuncSetAttribute(                                  \
-            (const void*)k_decode_attn_blk<GT, CH, NSEG>,                 \
+            (const void*)k_decode_attn_blk<GT, CH, NSEG, KVF>,            \
             hipFuncAttributeMaxDynamicSharedMemorySize,                   \
             blk_lds_bytes(GT, CH, NSEG));
     BLK_INSTANCES(BLK_PREPARE)
 #undef BLK_PREPARE
     return (int)hipErrorInvalidValue;
+}
+
+template <int KVF>
+static int blk_launch(
+    void* out, const void* q, const void* kpool, const void* vpool,
+    const void* page_table, const void* slot_ids, const void* seq_lens,
+    int S, int Hq, int KVH, int page, int max_pages, float scale,
+    int64_t q_stride, int split, int window, int chunk, int fragout,
+    hipStream_t stream)
+{
+    typedef const typename KvFmt<KVF>::elem* pool_t;
+    const int G = Hq / KVH;
+    dim3 grid(S, KVH);
+#define BLK_LAUNCH(GT, CH, NSEG)                                          \
+    if (G == GT && chunk == CH && split == NSEG) {                        \
+        k_decode_attn_blk<GT, CH, NSEG, KVF>                              \
+            <<<grid, NSEG * GT * 64, blk_lds_bytes(GT, CH, NSEG), stream>>>( \
+            (bf16*)out, (const bf16*)q, (pool_t)kpool, (pool_t)vpool,     \
+            (const int*)page_table,                                       \
+            (const int*)slot_ids, (const int*)seq_lens, Hq, KVH, page,    \
+            max_pages, scale, q_stride, window, fragout);                 \
+        return (int)hipGetLastError();                                    \
+    }
+    BLK_INSTANCES(BLK_LAUNCH)
+#undef BLK_LAUNCH
+    return (int)hipErrorInvalidValue;
+}
+
+extern "C" int decode_attn_blk_prepare(int G, int chunk, int split)
+{
+    return blk_prepare<0>(G, chunk, split);
 }
 
 extern "C" int decode_attn_blk_bf16(
@@ -132,19 +168,40 @@ extern "C" int decode_attn_blk_bf16(
     int64_t q_stride, int split, int window, int chunk, int fragout,
     hipStream_t stream)
 {
-    const int G = Hq / KVH;
-    dim3 grid(S, KVH);
-#define BLK_LAUNCH(GT, CH, NSEG)                                          \
-    if (G == GT && chunk == CH && split == NSEG) {                        \
-        k_decode_attn_blk<GT, CH, NSEG>                                   \
-            <<<grid, NSEG * GT * 64, blk_lds_bytes(GT, CH, NSEG), stream>>>( \
-            (bf16*)out, (const bf16*)q, (const bf16*)kpool,               \
-            (const bf16*)vpool, (const int*)page_table,                   \
-            (const int*)slot_ids, (const int*)seq_lens, Hq, KVH, page,    \
-            max_pages, scale, q_stride, window, fragout);                 \
-        return (int)hipGetLastError();                                    \
-    }
-    BLK_INSTANCES(BLK_LAUNCH)
-#undef BLK_LAUNCH
-    return (int)hipErrorInvalidValue;
+    return blk_launch<0>(out, q, kpool, vpool, page_table, slot_ids,
+                         seq_lens, S, Hq, KVH, page, max_pages, scale,
+                         q_stride, split, window, chunk, fragout, stream);
+}
+
+// ---- e4m3 KV pools ----
+extern "C" int decode_attn_blk_prepare_kv8(int G, int chunk, int split)
+{
+    return blk_prepare<1>(G, chunk, split);
+}
+
+extern "C" int decode_attn_blk_kv8(
+    void* out, const void* q, const void* kpool, const void* vpool,
+    const void* page_table, const void* slot_ids, const void* seq_lens,
+    int S, int Hq, int KVH, int page, int max_pages, float scale,
+    int64_t q_stride, int split, int window, int chunk, int fragout,
+    hipStream_t stream)
+{
+    return blk_launch<1>(out, q, kpool, vpool, page_table, slot_ids,
+                         seq_lens, S, Hq, KVH, page, max_pages, scale,
+                         q_stride, split, window, chunk, fragout, stream);
+}
+
+// one block per segment + k_decode_combine; sem must be null (the in-launch
+// combine is not instantiated for e4m3 pools)
+extern "C" int decode_attn_kv8(
+    void* out, void* o_part, void* ml_part, const void* q,
+    const void* kpool, const void* vpool, const void* page_table,
+    const void* slot_ids, const void* seq_lens, int S, int Hq, int KVH,
+    int page, int max_pages, float scale, int64_t q_stride, int split,
+    int window, int chunk, void* sem, int fragout, hipStream_t stream)
+{
+    return decode_attn_launch<1>(
+        out, o_part, ml_part, q, kpool, vpool, page_table, slot_ids,
+        seq_lens, S, Hq, KVH, page, max_pages, scale, q_stride, split,
+        window, chunk, sem, fragout, stream);
 }

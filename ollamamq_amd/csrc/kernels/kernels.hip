@@ -153,13 +153,35 @@ extern "C" int rope_bf16(
 // Paged-KV append: scatter k/v [T,KVH,D] to pool[layer] at (slot,pos).
 // Pool layout and addressing: common.cuh paged_kv_row.  One wave per
 // (token, head); lane moves 2 elems (D=128).
+// kv8: the pools hold e4m3fn codes (common.cuh KvFmt<1>, store rule
+// bf16_to_e4m3); kp/vp are then byte pools and a row is 128 bytes.
 // ---------------------------------------------------------------------------
+// A wave stores one 64-code run: lane holds the code of element `lane`;
+// eight lanes' codes travel as one 8-byte store.  Whole wave must call.
+DEV void wave_store_e4m3(uint8_t* run, int lane, unsigned c) {
+    unsigned w = c | (__shfl_down(c, 1, 64) << 8);
+    w |= __shfl_down(w, 2, 64) << 16;
+    const unsigned h = __shfl_down(w, 4, 64);
+    if ((lane & 7) == 0)
+        *reinterpret_cast<uint2*>(run + lane) = make_uint2(w, h);
+}
+
+// Same for a 128-code row of which lane holds elements (2*lane, 2*lane+1)
+// as two codes in the low 16 bits of c2.
+DEV void wave_store_e4m3x2(uint8_t* row, int lane, unsigned c2) {
+    const unsigned w = c2 | (__shfl_down(c2, 1, 64) << 16);
+    const unsigned h = __shfl_down(w, 2, 64);
+    if ((lane & 3) == 0)
+        *reinterpret_cast<uint2*>(row + 2 * lane) = make_uint2(w, h);
+}
+
 __global__ __launch_bounds__(256) void k_kv_append(
     bf16* __restrict__ kp, bf16* __restrict__ vp,
     const bf16* __restrict__ k, const bf16* __restrict__ v,
     const int* __restrict__ slot, const int* __restrict__ pos,
     const int* __restrict__ page_table,
-    int T, int KVH, int D, int page, int max_pages, int64_t src_stride)
+    int T, int KVH, int D, int page, int max_pages, int64_t src_stride,
+    int kv8)
 {
     const int gid = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -170,8 +192,31 @@ __global__ __launch_bounds__(256) void k_kv_append(
     const int64_t src = (int64_t)t * src_stride + (int64_t)h * D;
     const bf162* ks = reinterpret_cast<const bf162*>(k + src);
     const bf162* vs = reinterpret_cast<const bf162*>(v + src);
+    if (kv8) {                           // wave-uniform (kernel argument)
+        const unsigned* kw = reinterpret_cast<const unsigned*>(ks);
+        const unsigned* vw = reinterpret_cast<const unsigned*>(vs);
+        wave_store_e4m3x2(reinterpret_cast<uint8_t*>(kp) + dst, lane,
+                          bf16x2_to_e4m3x2(kw[lane]));
+        wave_store_e4m3x2(reinterpret_cast<uint8_t*>(vp) + dst, lane,
+                          bf16x2_to_e4m3x2(vw[lane]));
+        return;
+    }
     reinterpret_cast<bf162*>(kp + dst)[lane] = ks[lane];
     reinterpret_cast<bf162*>(vp + dst)[lane] = vs[lane];
+}
+
+static int kv_append_launch(
+    void* kp, void* vp, const void* k, const void* v, const void* slot,
+    const void* pos, const void* page_table, int T, int KVH, int D,
+    int page, int max_pages, int64_t src_stride, int kv8,
+    hipStream_t stream)
+{
+    const int waves = T * KVH;
+    k_kv_append<<<(waves + 3) / 4, 256, 0, stream>>>(
+        (bf16*)kp, (bf16*)vp, (const bf16*)k, (const bf16*)v,
+        (const int*)slot, (const int*)pos, (const int*)page_table,
+        T, KVH, D, page, max_pages, src_stride, kv8);
+    return (int)hipGetLastError();
 }
 
 extern "C" int kv_append_bf16(
@@ -179,12 +224,18 @@ extern "C" int kv_append_bf16(
     const void* pos, const void* page_table, int T, int KVH, int D,
     int page, int max_pages, int64_t src_stride, hipStream_t stream)
 {
-    const int waves = T * KVH;
-    k_kv_append<<<(waves + 3) / 4, 256, 0, stream>>>(
-        (bf16*)kp, (bf16*)vp, (const bf16*)k, (const bf16*)v,
-        (const int*)slot, (const int*)pos, (const int*)page_table,
-        T, KVH, D, page, max_pages, src_stride);
-    return (int)hipGetLastError();
+    return kv_append_launch(kp, vp, k, v, slot, pos, page_table, T, KVH, D,
+                            page, max_pages, src_stride, 0, stream);
+}
+
+// the same append into e4m3 pools (k, v stay bf16)
+extern "C" int kv_append_kv8(
+    void* kp, void* vp, const void* k, const void* v, const void* slot,
+    const void* pos, const void* page_table, int T, int KVH, int D,
+    int page, int max_pages, int64_t src_stride, hipStream_t stream)
+{
+    return kv_append_launch(kp, vp, k, v, slot, pos, page_table, T, KVH, D,
+                            page, max_pages, src_stride, 1, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -593,7 +644,7 @@ __global__ __launch_bounds__(256) void k_rope_append(
     const int* __restrict__ page_table,
     const float* __restrict__ cost, const float* __restrict__ sint,
     int T, int Hq, int KVH, int D, int page, int max_pages,
-    int64_t qs, int64_t ks, int64_t vs)
+    int64_t qs, int64_t ks, int64_t vs, int kv8)
 {
     const int gid = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -629,6 +680,14 @@ __global__ __launch_bounds__(256) void k_rope_append(
         const bf16 hi = f2bf(x2 * c + x1 * s);
         base[lane] = lo;
         base[lane + d2] = hi;
+        if (kv8) {                       // e4m3 pool: row is 128 bytes
+            uint8_t* dst8 = reinterpret_cast<uint8_t*>(kp) + row;
+            wave_store_e4m3(dst8, lane,
+                            bf16_to_e4m3(__bfloat16_as_ushort(lo)));
+            wave_store_e4m3(dst8 + d2, lane,
+                            bf16_to_e4m3(__bfloat16_as_ushort(hi)));
+            return;
+        }
         dst[lane] = lo;
         dst[lane + d2] = hi;
         return;
@@ -637,9 +696,32 @@ __global__ __launch_bounds__(256) void k_rope_append(
         const int vh = h - Hq - KVH;
         const bf162* src = reinterpret_cast<const bf162*>(
             v + (int64_t)t * vs + (int64_t)vh * D);
+        if (kv8) {
+            wave_store_e4m3x2(
+                reinterpret_cast<uint8_t*>(vp) + row, lane,
+                bf16x2_to_e4m3x2(
+                    reinterpret_cast<const unsigned*>(src)[lane]));
+            return;
+        }
         bf162* dst = reinterpret_cast<bf162*>(vp + row);
         dst[lane] = src[lane];
     }
+}
+
+static int rope_append_launch(
+    void* q, void* k, const void* v, void* kp, void* vp, const void* pos,
+    const void* slot, const void* page_table, const void* cost,
+    const void* sint, int T, int Hq, int KVH, int D, int page,
+    int max_pages, int64_t qs, int64_t ks, int64_t vs, int kv8,
+    hipStream_t stream)
+{
+    const int waves = T * (Hq + 2 * KVH);
+    k_rope_append<<<(waves + 3) / 4, 256, 0, stream>>>(
+        (bf16*)q, (bf16*)k, (const bf16*)v, (bf16*)kp, (bf16*)vp,
+        (const int*)pos, (const int*)slot, (const int*)page_table,
+        (const float*)cost, (const float*)sint,
+        T, Hq, KVH, D, page, max_pages, qs, ks, vs, kv8);
+    return (int)hipGetLastError();
 }
 
 extern "C" int rope_append_bf16(
@@ -648,13 +730,21 @@ extern "C" int rope_append_bf16(
     const void* sint, int T, int Hq, int KVH, int D, int page,
     int max_pages, int64_t qs, int64_t ks, int64_t vs, hipStream_t stream)
 {
-    const int waves = T * (Hq + 2 * KVH);
-    k_rope_append<<<(waves + 3) / 4, 256, 0, stream>>>(
-        (bf16*)q, (bf16*)k, (const bf16*)v, (bf16*)kp, (bf16*)vp,
-        (const int*)pos, (const int*)slot, (const int*)page_table,
-        (const float*)cost, (const float*)sint,
-        T, Hq, KVH, D, page, max_pages, qs, ks, vs);
-    return (int)hipGetLastError();
+    return rope_append_launch(q, k, v, kp, vp, pos, slot, page_table, cost,
+                              sint, T, Hq, KVH, D, page, max_pages, qs, ks,
+                              vs, 0, stream);
+}
+
+// the same into e4m3 pools: q and k come back rotated bf16 as above
+extern "C" int rope_append_kv8(
+    void* q, void* k, const void* v, void* kp, void* vp, const void* pos,
+    const void* slot, const void* page_table, const void* cost,
+    const void* sint, int T, int Hq, int KVH, int D, int page,
+    int max_pages, int64_t qs, int64_t ks, int64_t vs, hipStream_t stream)
+{
+    return rope_append_launch(q, k, v, kp, vp, pos, slot, page_table, cost,
+                              sint, T, Hq, KVH, D, page, max_pages, qs, ks,
+                              vs, 1, stream);
 }
 
 // ---------------------------------------------------------------------------

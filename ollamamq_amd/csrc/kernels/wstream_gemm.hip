@@ -134,7 +134,21 @@ struct RopeEpi {
     bf16* kp;             // this layer's K pool base
     bf16* vp;
     int nl, nkl, psz, maxp;
+    int kv8;              // pools hold e4m3 codes (common.cuh KvFmt<1>):
+                          // kp/vp are byte pools, the store rule is
+                          // bf16_to_e4m3 of the bf16 the bf16 pool gets
 };
+
+// one element of a pool row: the bf16 itself, or its e4m3 code (kv8, a
+// kernel argument, so the branch is uniform)
+DEV void pool_store(bf16* pool, int64_t off, float x, int kv8) {
+    const bf16 b = __float2bfloat16(x);
+    if (kv8)
+        reinterpret_cast<uint8_t*>(pool)[off] =
+            (uint8_t)bf16_to_e4m3(__bfloat16_as_ushort(b));
+    else
+        pool[off] = b;
+}
 
 // Spill one wave's 32x32 fp32 accumulator tile (MFMA C layout: col =
 // lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)) to its red8 slab for the
@@ -484,11 +498,11 @@ __global__ __launch_bounds__(512) void k_wstream_gemm(
                         qr[d0 + c] = __float2bfloat16(rlo);
                         qr[64 + d0 + c] = __float2bfloat16(rhi);
                     } else {               // k: rotated, straight to pool
-                        bf16* dst = rp.kp + paged_kv_row(
+                        const int64_t dst = paged_kv_row(
                             rp.ptab, rp.slot[gm], rp.maxp, p, rp.psz,
                             rp.nkl, head);
-                        dst[d0 + c] = __float2bfloat16(rlo);
-                        dst[64 + d0 + c] = __float2bfloat16(rhi);
+                        pool_store(rp.kp, dst + d0 + c, rlo, rp.kv8);
+                        pool_store(rp.kp, dst + 64 + d0 + c, rhi, rp.kv8);
                     }
                 }
             } else {
@@ -510,10 +524,10 @@ __global__ __launch_bounds__(512) void k_wstream_gemm(
                         if (rstd_parts) sv *= rstd_sh[gm];
                         if (bias)
                             sv += __bfloat162float(bias[t * 32 + n]);
-                        bf16* dst = rp.vp + paged_kv_row(
+                        const int64_t dst = paged_kv_row(
                             rp.ptab, rp.slot[gm], rp.maxp, rp.pos[gm],
                             rp.psz, rp.nkl, head);
-                        dst[d0 + n] = __float2bfloat16(sv);
+                        pool_store(rp.vp, dst + d0 + n, sv, rp.kv8);
                     }
                 }
             }
@@ -770,18 +784,18 @@ extern "C" int wstream_gemm_bf16(
 
 // qkv GEMM with fused RoPE + paged KV append (fused decode chain):
 // q lands rotated in y's standard layout; k/v land in the paged pool.
-extern "C" int wstream_qkv_rope_bf16(
+static int wstream_qkv_rope_launch(
     void* y, const void* x, const void* wp, const void* bias,
     int M, int N, int K, int64_t xs,
     const void* rstd_parts, int rstd_nt, float inv_h, float eps,
     const void* rcos, const void* rsin, const void* pos,
     const void* slot, const void* ptab, void* kp, void* vp,
     int nl, int nkl, int psz, int maxp, int xf, const void* wscale,
-    hipStream_t stream)
+    int kv8, hipStream_t stream)
 {
     const RopeEpi rp{(const float*)rcos, (const float*)rsin,
                      (const int*)pos, (const int*)slot, (const int*)ptab,
-                     (bf16*)kp, (bf16*)vp, nl, nkl, psz, maxp};
+                     (bf16*)kp, (bf16*)vp, nl, nkl, psz, maxp, kv8};
     const WsArgs a{y, nullptr, x, wp, bias, M, N, K, xs, 1,
                    rstd_parts, rstd_nt, inv_h, eps, nullptr, nullptr, rp,
                    0, wscale};
@@ -792,4 +806,35 @@ extern "C" int wstream_qkv_rope_bf16(
     else
         ws_launch<1, 1, 0, 0, 1>(a, stream);
     return (int)hipGetLastError();
+}
+
+extern "C" int wstream_qkv_rope_bf16(
+    void* y, const void* x, const void* wp, const void* bias,
+    int M, int N, int K, int64_t xs,
+    const void* rstd_parts, int rstd_nt, float inv_h, float eps,
+    const void* rcos, const void* rsin, const void* pos,
+    const void* slot, const void* ptab, void* kp, void* vp,
+    int nl, int nkl, int psz, int maxp, int xf, const void* wscale,
+    hipStream_t stream)
+{
+    return wstream_qkv_rope_launch(
+        y, x, wp, bias, M, N, K, xs, rstd_parts, rstd_nt, inv_h, eps, rcos,
+        rsin, pos, slot, ptab, kp, vp, nl, nkl, psz, maxp, xf, wscale, 0,
+        stream);
+}
+
+// the same GEMM appending into e4m3 KV pools (either weight pack)
+extern "C" int wstream_qkv_rope_kv8(
+    void* y, const void* x, const void* wp, const void* bias,
+    int M, int N, int K, int64_t xs,
+    const void* rstd_parts, int rstd_nt, float inv_h, float eps,
+    const void* rcos, const void* rsin, const void* pos,
+    const void* slot, const void* ptab, void* kp, void* vp,
+    int nl, int nkl, int psz, int maxp, int xf, const void* wscale,
+    hipStream_t stream)
+{
+    return wstream_qkv_rope_launch(
+        y, x, wp, bias, M, N, K, xs, rstd_parts, rstd_nt, inv_h, eps, rcos,
+        rsin, pos, slot, ptab, kp, vp, nl, nkl, psz, maxp, xf, wscale, 1,
+        stream);
 }

@@ -4,6 +4,10 @@ Layout [L, n_pages, KVH, page_size, D]: one (page, kv-head) is a contiguous
 page_size*D*2B run (4 KiB at page=16, D=128), the unit the decode-attention
 kernel streams with wide vector loads.  Page tables are int32 per slot.
 
+kv_quant="fp8" stores both pools as OCP e4m3fn codes at unit scale
+(torch.uint8, same shape, 2 KiB per (page, kv-head)): the writers encode
+with ops/quant.py kv_fp8_encode's rule, the readers decode exactly.
+
 The reference has no KV concept (its context handling is only plumbing the
 `num_ctx` option to Ollama, reference src/control.rs:804-806); the paged pool
 is this framework's realization of "model loaded with context N" — "load"
@@ -28,7 +32,15 @@ class PagedKVCache:
         max_ctx: int = 8192,
         device: str = "cpu",
         dtype: torch.dtype = torch.float32,
+        kv_quant: str = "",
     ):
+        if kv_quant not in ("", "fp8"):
+            raise ValueError(f"PagedKVCache: unknown kv_quant {kv_quant!r} "
+                             "(\"\" or \"fp8\")")
+        self.kv_quant = kv_quant
+        self.kv_fp8 = kv_quant == "fp8"
+        if self.kv_fp8:
+            dtype = torch.uint8
         self.page_size = page_size
         self.head_dim = head_dim
         self.n_kv_heads = n_kv_heads

@@ -76,6 +76,9 @@ class TPWorker(worker_mod.Worker):
         if cfg.n_heads % self.world or \
                 (cfg.n_kv_heads % self.world and self.world > cfg.n_kv_heads):
             return f"model {model} heads not divisible by TP={self.world}"
+        kv_quant, err = worker_mod.kv_quant_from_env()
+        if err:
+            return err
         ctx = min(num_ctx or self.default_ctx, cfg.max_ctx)
         try:
             if torch.cuda.is_available():
@@ -87,7 +90,7 @@ class TPWorker(worker_mod.Worker):
             kv = PagedKVCache.for_model(
                 cfg, tp_size=self.world, n_pages=pages,
                 max_slots=self.max_batch + 2, max_ctx=ctx,
-                device=self.device, dtype=self.dtype)
+                device=self.device, dtype=self.dtype, kv_quant=kv_quant)
             eng = LlamaEngine(m, kv, max_batch=self.max_batch)
             # lockstep capture: every rank reaches warm_graphs at the same
             # op, so the in-graph RCCL collectives pair up across ranks

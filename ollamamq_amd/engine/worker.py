@@ -44,6 +44,15 @@ from .tokenizer import ByteTokenizer
 VERSION = "0.1.0-ollamamq-amd"
 
 
+def kv_quant_from_env():
+    """OLLAMAMQ_KV_CACHE_TYPE -> (kv_quant, error text or None): unset or
+    "bf16" is the unquantised pool, "fp8" the e4m3 pool."""
+    v = os.environ.get("OLLAMAMQ_KV_CACHE_TYPE", "")
+    if v in ("", "bf16", "fp8"):
+        return ("fp8" if v == "fp8" else ""), None
+    return "", f"unknown KV cache type: {v} (bf16 or fp8)"
+
+
 class Worker:
     def __init__(self, gpu: int, max_batch: int = 32,
                  default_ctx: int = 4096, models: Optional[list] = None):
@@ -87,6 +96,9 @@ class Worker:
             cfg = PRESETS.get(model)
             if cfg is None:
                 return f"unknown model: {model}"
+            kv_quant, err = kv_quant_from_env()
+            if err:
+                return err
             ctx = min(num_ctx or self.default_ctx, cfg.max_ctx)
             try:
                 if torch.cuda.is_available():
@@ -96,7 +108,8 @@ class Worker:
                 pages = (self.max_batch + 2) * ((ctx + 15) // 16 + 2)
                 kv = PagedKVCache.for_model(
                     cfg, n_pages=pages, max_slots=self.max_batch + 2,
-                    max_ctx=ctx, device=self.device, dtype=self.dtype)
+                    max_ctx=ctx, device=self.device, dtype=self.dtype,
+                    kv_quant=kv_quant)
                 eng = LlamaEngine(m, kv, max_batch=self.max_batch)
                 # pre-capture: no first-request jitter.  The penalised
                 # twins double the graph set, so they are opt-in and

@@ -68,6 +68,18 @@ def _signatures():
     }
 
 
+# entry points over an e4m3 KV cache: same arguments as their bf16-pool twin
+_KV8_TWINS = {
+    "kv_append_kv8": "kv_append_bf16",
+    "rope_append_kv8": "rope_append_bf16",
+    "wstream_qkv_rope_kv8": "wstream_qkv_rope_bf16",
+    "decode_attn_kv8": "decode_attn_bf16",
+    "decode_attn_blk_prepare_kv8": "decode_attn_blk_prepare",
+    "decode_attn_blk_kv8": "decode_attn_blk_bf16",
+    "prefill_attn_kv8": "prefill_attn_bf16",
+}
+
+
 def _try_load():
     global _lib, _load_err
     if _lib is not None or _load_err is not None:
@@ -77,7 +89,9 @@ def _try_load():
     except OSError as e:
         _load_err = f"cannot load {_LIB_PATH}: {e}"
         return
-    for name, argtypes in _signatures().items():
+    sigs = _signatures()
+    sigs.update({k8: sigs[k] for k8, k in _KV8_TWINS.items()})
+    for name, argtypes in sigs.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = ctypes.c_int       # every entry point returns hipError
@@ -186,12 +200,34 @@ def rope(q, k, positions, cos, sin):
                           _stream()), "rope")
 
 
+def _kv8(cache, op):
+    """True for an fp8 KV cache, whose pools must be what the *_kv8 entry
+    points address: contiguous uint8."""
+    if not getattr(cache, "kv_fp8", False):
+        return False
+    for t in (cache.k_pool, cache.v_pool):
+        if t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError(f"{op}: an fp8 KV cache needs contiguous uint8 "
+                             f"pools, got {t.dtype}")
+    return True
+
+
+def _bf16_rows(op, **tensors):
+    for name, t in tensors.items():
+        if t.dtype != torch.bfloat16:
+            raise ValueError(f"{op}: {name} must be bf16, got {t.dtype}")
+
+
 def kv_append(cache, layer, k, v, slot_ids, positions):
     T, KVH, D = k.shape
+    kv8 = _kv8(cache, "kv_append")
+    if kv8:
+        _bf16_rows("kv_append", k=k, v=v)
     kp, vp = _layer_ptrs(cache, layer)
     pos32, slot32 = _i32(positions), _i32(slot_ids)
     assert _row_stride(k, D) == _row_stride(v, D)
-    _check(_lib.kv_append_bf16(kp, vp, _p(k), _p(v), _p(slot32), _p(pos32),
+    fn = _lib.kv_append_kv8 if kv8 else _lib.kv_append_bf16
+    _check(fn(kp, vp, _p(k), _p(v), _p(slot32), _p(pos32),
                                _p(cache.page_table), T, KVH, D,
                                cache.page_size, cache.page_table.shape[1],
                                _row_stride(k, D), _stream()), "kv_append")
@@ -202,9 +238,13 @@ def rope_append(cache, layer, q, k, v, positions, slot_ids, cos, sin):
     T, Hq, D = q.shape
     KVH = k.shape[1]
     assert D == 128
+    kv8 = _kv8(cache, "rope_append")
+    if kv8:
+        _bf16_rows("rope_append", q=q, k=k, v=v)
     kp, vp = _layer_ptrs(cache, layer)
     pos32, slot32 = _i32(positions), _i32(slot_ids)
-    _check(_lib.rope_append_bf16(
+    fn = _lib.rope_append_kv8 if kv8 else _lib.rope_append_bf16
+    _check(fn(
         _p(q), _p(k), _p(v), kp, vp, _p(pos32), _p(slot32),
         _p(cache.page_table), _p(cos), _p(sin), T, Hq, KVH, D,
         cache.page_size, cache.page_table.shape[1],
@@ -267,7 +307,11 @@ def _prefill_launch(out, q, cache, layer, plan, window):
     if n_tiles == 0:
         return
     kp, vp = _layer_ptrs(cache, layer)
-    _check(_lib.prefill_attn_bf16(
+    fn = _lib.prefill_attn_bf16
+    if _kv8(cache, "prefill_attn"):
+        _bf16_rows("prefill_attn", q=q)
+        fn = _lib.prefill_attn_kv8
+    _check(fn(
         _p(out), _p(q), kp, vp, _p(cache.page_table),
         _p(tile_slot), _p(tile_q0), _p(tile_pos0), _p(tile_rows),
         n_tiles, Hq, cache.n_kv_heads, cache.page_size,
@@ -278,6 +322,9 @@ def _prefill_launch(out, q, cache, layer, plan, window):
 def _attention(q, cache, layer, meta, qt):
     T, Hq, D = q.shape
     assert D == 128
+    if getattr(cache, "kv_fp8", False):
+        raise ValueError("the VALU paged_attn path (OLLAMAMQ_VALU_PREFILL=1) "
+                         "has no fp8 KV cache instantiation")
     out = torch.empty_like(q)
     kp, vp = _layer_ptrs(cache, layer)
     tile_slot, tile_q0, tile_pos0, tile_rows = _attn_plan(cache, meta, qt)
@@ -366,14 +413,16 @@ def decode_blocksplit(S, KVH, G, chunk, split, env=None):
 _blk_ready = {}
 
 
-def _blk_prepare(G, chunk, split):
+def _blk_prepare(G, chunk, split, kv8=False):
     """Opt one instantiation in to its dynamic LDS size (above 64 KB at
     G = 4, split 4), once.  False when the runtime refuses it: the caller
     keeps the two-kernel path."""
-    key = (G, chunk, split)
+    key = (G, chunk, split, bool(kv8))
     ok = _blk_ready.get(key)
     if ok is None:
-        err = _lib.decode_attn_blk_prepare(G, chunk, split)
+        prep = _lib.decode_attn_blk_prepare_kv8 if kv8 \
+            else _lib.decode_attn_blk_prepare
+        err = prep(G, chunk, split)
         ok = _blk_ready[key] = err == 0
         if not ok:
             import warnings
@@ -392,9 +441,18 @@ def attention_decode(q, cache, layer, meta, fragout=False):
     o GEMM streams it linearly like packed weights).
     Where decode_blocksplit() says so, the split's segments share one
     block per (sequence, kv-head) and merge in LDS (k_decode_attn_blk):
-    same arithmetic, bit-identical output, no partials, one launch."""
+    same arithmetic, bit-identical output, no partials, one launch.
+    An fp8 KV cache runs the e4m3 instantiations of the same two kernels
+    (same split and chunk rules); it has no in-launch combine."""
     S, Hq, D = q.shape
     assert D == 128
+    kv8 = _kv8(cache, "attention_decode")
+    if kv8:
+        _bf16_rows("attention_decode", q=q)
+        if os.environ.get("OLLAMAMQ_FUSED_COMBINE") == "1":
+            raise ValueError("attention_decode: the in-launch combine "
+                             "(OLLAMAMQ_FUSED_COMBINE=1) has no fp8 KV "
+                             "cache instantiation")
     out = torch.empty((((S + 31) // 32) * 32 * Hq * D,)
                       if fragout else (S, Hq, D),
                       dtype=q.dtype, device=q.device)
@@ -412,9 +470,10 @@ def attention_decode(q, cache, layer, meta, fragout=False):
     G, chunk = Hq // kvh, _decode_chunk(Hq // kvh)
     slot32, len32 = _i32(meta.slot_ids), _i32(meta.seq_lens)
     if decode_blocksplit(S, kvh, G, chunk, split) \
-            and _blk_prepare(G, chunk, split):
+            and _blk_prepare(G, chunk, split, kv8):
         # one block per (sequence, kv-head); no partial scratch
-        _check(_lib.decode_attn_blk_bf16(
+        fn = _lib.decode_attn_blk_kv8 if kv8 else _lib.decode_attn_blk_bf16
+        _check(fn(
             _p(out), _p(q), kp, vp, _p(cache.page_table),
             _p(slot32), _p(len32), S, Hq, kvh, cache.page_size,
             cache.page_table.shape[1], 1.0 / (D ** 0.5), _row_stride(q, D),
@@ -434,7 +493,8 @@ def attention_decode(q, cache, layer, meta, fragout=False):
         # fewer, longer blocks.
         if os.environ.get("OLLAMAMQ_FUSED_COMBINE") == "1":
             sem = _p(_combine_sem(S, kvh, q.device))
-    _check(_lib.decode_attn_bf16(
+    fn = _lib.decode_attn_kv8 if kv8 else _lib.decode_attn_bf16
+    _check(fn(
         _p(out), op, mp, _p(q), kp, vp, _p(cache.page_table),
         _p(slot32), _p(len32), S, Hq, kvh, cache.page_size,
         cache.page_table.shape[1], 1.0 / (D ** 0.5), _row_stride(q, D),
@@ -688,7 +748,11 @@ def linear_qkv_rope(x, packed, N, bias_rp, cache, layer, positions,
     kp, vp = _layer_ptrs(cache, layer)
     pos32, slot32 = _i32(positions), _i32(slots)
     wbuf, wscale = _wfmt(packed)
-    _check(_lib.wstream_qkv_rope_bf16(
+    fn = _lib.wstream_qkv_rope_bf16
+    if _kv8(cache, "linear_qkv_rope"):
+        _bf16_rows("linear_qkv_rope", x=x)
+        fn = _lib.wstream_qkv_rope_kv8
+    _check(fn(
         _p(y), _p(x), _p(wbuf), _p(bias_rp), M, N, K, xs,
         _p(rstd), rstd_nt, float(inv_h), float(eps),
         _p(cos), _p(sin), _p(pos32), _p(slot32), _p(cache.page_table),
@@ -1081,6 +1145,9 @@ def sample(logits, temperature, top_k, top_p, generator=None):
 def decode_pure(cache, layer, meta, split, chunk=64):
     """Staging-only diagnostic for decode attention (see decode_attn.hip
     k_decode_pure)."""
+    if getattr(cache, "kv_fp8", False):
+        raise ValueError("decode_pure: the KV-stream probe is instantiated "
+                         "for bf16 pools only")
     sink = torch.zeros(1, dtype=torch.float32, device=cache.k_pool.device)
     kp, vp = _layer_ptrs(cache, layer)
     S = meta.slot_ids.shape[0]

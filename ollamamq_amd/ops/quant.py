@@ -73,3 +73,29 @@ def dequantize_fp8_weight(w):
     """The model-build transform: w replaced by its fp8-dequantised values
     (same shape and dtype)."""
     return quantize_fp8(w)[2]
+
+
+# ---------------------------------------------------------------------------
+# FP8 KV cache: the pools hold e4m3fn codes at unit scale.
+
+
+def kv_fp8_encode(x):
+    """The KV store rule, any float tensor -> uint8 codes: clamp to +-448
+    (so +-inf store +-448), round to the nearest e4m3fn value, ties to
+    even; -0.0 keeps its sign; a NaN stores 0x7f with its sign.  The HIP
+    writers spell the same rule in integers (common.cuh bf16_to_e4m3)."""
+    f = x.float()
+    nan = torch.isnan(f)
+    u = torch.where(nan, torch.zeros_like(f), f).clamp(-FP8_MAX, FP8_MAX)
+    codes = e4m3_encode(e4m3_round(u))
+    nan_code = (((f.view(torch.int32) >> 24) & 0x80) | 0x7F).to(torch.uint8)
+    return torch.where(nan, nan_code, codes)
+
+
+def kv_fp8_decode(codes, dtype=torch.float32):
+    """The KV load rule: a code's exact value (exact in bf16 as well); the
+    NaN codes 0x7f / 0xff decode to NaN."""
+    v = e4m3_decode(codes)
+    v = torch.where((codes & 0x7F) == 0x7F, torch.full_like(v, float("nan")),
+                    v)
+    return v.to(dtype)

@@ -9,6 +9,8 @@ from __future__ import annotations
 
 import torch
 
+from .quant import kv_fp8_decode, kv_fp8_encode
+
 
 def rmsnorm_residual(x, residual, weight, eps):
     """y = rmsnorm(x + residual) * weight; returns (y, x + residual).
@@ -45,10 +47,15 @@ def rope(q, k, positions, cos, sin):
 
 
 def kv_append(cache, layer, k, v, slot_ids, positions):
-    """Scatter k/v [T, KVH, D] into the paged pool at (slot, position)."""
+    """Scatter k/v [T, KVH, D] into the paged pool at (slot, position).
+    An fp8 cache stores the e4m3 code of each value (quant.kv_fp8_encode)."""
     ps = cache.page_size
     pages = cache.page_table[slot_ids.long(), (positions // ps).long()]
     offs = (positions % ps).long()
+    if getattr(cache, "kv_fp8", False):
+        cache.k_pool[layer, pages.long(), :, offs] = kv_fp8_encode(k)
+        cache.v_pool[layer, pages.long(), :, offs] = kv_fp8_encode(v)
+        return
     cache.k_pool[layer, pages.long(), :, offs] = k.to(cache.k_pool.dtype)
     cache.v_pool[layer, pages.long(), :, offs] = v.to(cache.v_pool.dtype)
 
@@ -60,6 +67,8 @@ def _gather_kv(cache, layer, slot, kv_len):
     pages = cache.page_table[slot, :n_pages].long()
     k = cache.k_pool[layer, pages]  # [n_pages, KVH, ps, D]
     v = cache.v_pool[layer, pages]
+    if getattr(cache, "kv_fp8", False):
+        k, v = kv_fp8_decode(k), kv_fp8_decode(v)
     k = k.permute(0, 2, 1, 3).reshape(n_pages * ps, -1, cache.head_dim)
     v = v.permute(0, 2, 1, 3).reshape(n_pages * ps, -1, cache.head_dim)
     return k[:kv_len], v[:kv_len]

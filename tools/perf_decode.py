@@ -1,7 +1,12 @@
 """Microbench: decode attention old (unsplit) vs flash-decoding path
 (two-kernel split and block-split).
 
-Run on a GPU box:  python tools/perf_decode.py [ctx] [batch]
+Run on a GPU box:  python tools/perf_decode.py [ctx] [batch] [--kv fp8]
+
+--kv fp8 adds the same two paths over an e4m3 KV cache of the same geometry
+(ops/quant.py kv_fp8_encode of the bf16 pools), in the same run; TB/s counts
+the bytes each format really reads.  Every line is the median of three
+repeats with min..max.
 """
 import os
 import sys
@@ -18,6 +23,9 @@ from ollamamq_amd.ops import hip
 
 def main():
     hip.require()
+    kv8 = "--kv" in sys.argv and sys.argv[sys.argv.index("--kv") + 1] == "fp8"
+    if "--kv" in sys.argv:
+        del sys.argv[sys.argv.index("--kv"):sys.argv.index("--kv") + 2]
     ctx = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
     B = int(sys.argv[2]) if len(sys.argv) > 2 else 32
     Hq_arg = int(sys.argv[3]) if len(sys.argv) > 3 else 32
@@ -46,17 +54,21 @@ def main():
 
     kv_bytes = B * KVH * ctx * D * 2 * 2
 
-    def bench(fn, label):
+    def bench(fn, label, nbytes=kv_bytes):
         for _ in range(5):
             out = fn(0)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        n = 64
-        for i in range(n):
-            out = fn(i % L)     # cycle layers: cold KV every call
-        torch.cuda.synchronize()
-        dt = (time.perf_counter() - t0) / n
-        print(f"{label}: {dt*1e6:8.1f} us  {kv_bytes/dt/1e12:6.2f} TB/s")
+        ts = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            n = 64
+            for i in range(n):
+                out = fn(i % L)     # cycle layers: cold KV every call
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) / n)
+        ts.sort()
+        print(f"{label}: {ts[1]*1e6:8.1f} us ({ts[0]*1e6:.1f}..{ts[2]*1e6:.1f})"
+              f"  {nbytes/ts[1]/1e12:6.2f} TB/s")
         return out
 
     def path(blk):
@@ -72,6 +84,19 @@ def main():
         assert torch.equal(o_blk, o_new), "block path differs from split"
     else:
         print(f"block : not instantiated for G={G} split={split}")
+    if kv8:
+        from ollamamq_amd.ops.quant import kv_fp8_encode
+        c8 = PagedKVCache(L, KVH, D, page_size=16, n_pages=n_pages,
+                          max_slots=B, max_ctx=ctx + 64, device=dev,
+                          kv_quant="fp8")
+        c8.page_table.copy_(cache.page_table)
+        for l in range(L):      # per layer: the fp32 temporaries are large
+            c8.k_pool[l] = kv_fp8_encode(cache.k_pool[l])
+            c8.v_pool[l] = kv_fp8_encode(cache.v_pool[l])
+        for blk, label in ((False, "split8"), (True, "block8")):
+            os.environ["OLLAMAMQ_DECODE_BLOCKSPLIT"] = "1" if blk else "0"
+            bench(lambda l: hip.attention_decode(q, c8, l, meta), label,
+                  kv_bytes // 2)
     os.environ["OLLAMAMQ_DECODE_BLOCKSPLIT"] = "0"
     for sp in (1, 2, 4, 8):
         bench(lambda l, sp=sp: hip.decode_pure(cache, l, meta, sp),

@@ -6,6 +6,8 @@ is Python/host bookkeeping that the GPU waits on.
 
   python tools/perf_step.py [model] [users] [--penalty] [--topk]
 
+OLLAMAMQ_KV_CACHE_TYPE=fp8 selects the e4m3 KV cache, as in the worker.
+
 --penalty measures the same step a second time in the same process with
 every row at repeat_penalty 1.1, repeat_last_n 64 (the penalised graph:
 the logit-penalty kernel between the forward and the sampling tail) and
@@ -90,11 +92,14 @@ def main():
     cfg = PRESETS[model_name]
     dev = "cuda"
     n_pages = (users + 2) * ((512 + 200 + 15) // 16 + 2)
+    from ollamamq_amd.engine.worker import kv_quant_from_env
+    kv_quant, err = kv_quant_from_env()
+    assert err is None, err
     model = LlamaModel(cfg, device=dev, dtype=torch.bfloat16, seed=1,
                        fast_init=True)
     kv = PagedKVCache.for_model(cfg, n_pages=n_pages, max_slots=users + 2,
                                 max_ctx=1024, device=dev,
-                                dtype=torch.bfloat16)
+                                dtype=torch.bfloat16, kv_quant=kv_quant)
     eng = LlamaEngine(model, kv, max_batch=users)
     full, replay = measure(eng, cfg, users, "plain")
     if penalty:
