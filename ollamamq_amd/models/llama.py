@@ -267,6 +267,7 @@ class LlamaModel:
         tp_size: int = 1,
         process_group=None,
         fast_init: bool = False,
+        fp8_resident: Optional[bool] = None,
     ):
         assert cfg.n_heads % tp_size == 0, "n_heads must divide TP"
         self.cfg = cfg
@@ -278,6 +279,16 @@ class LlamaModel:
         # KV-head replication when tp > n_kv_heads is not supported; shard.
         self.n_local_heads = cfg.n_heads // tp_size
         self.n_local_kv_heads = max(1, cfg.n_kv_heads // tp_size)
+        # pack-resident fp8 (None: OLLAMAMQ_FP8_RESIDENT=1): the fp8 packs
+        # become the only copy of every projection and of the LM head.
+        # Honoured for an fp8 config on cuda in bf16 only; _pack_weights
+        # clears it again when it cannot drop the live weights.
+        if fp8_resident is None:
+            import os
+            fp8_resident = os.environ.get("OLLAMAMQ_FP8_RESIDENT") == "1"
+        self.fp8_resident = bool(
+            fp8_resident and cfg.quant == "fp8"
+            and self.device.type == "cuda" and dtype == torch.bfloat16)
 
         gen_dev = "cuda" if (fast_init and self.device.type == "cuda") else "cpu"
         gen = torch.Generator(device=gen_dev)
@@ -333,8 +344,15 @@ class LlamaModel:
         import os
         if self.device.type != "cuda" or self.dtype != torch.bfloat16 \
                 or os.environ.get("OLLAMAMQ_NO_PACK") == "1":
+            self.fp8_resident = False
             return
         fp8 = self.cfg.quant == "fp8"
+        if self.fp8_resident:
+            self.fp8_resident = self._resident_fits()
+        if self.fp8_resident:
+            self._pack_resident()
+            self._enable_chain()
+            return
         if fp8:
             # fp8 packs are one byte per packed element (embed is not
             # packed): about half the bf16 copy.  (70B on one 288 GB GPU
@@ -387,8 +405,67 @@ class LlamaModel:
             self.lm_head_pk = None
             torch.cuda.empty_cache()
             return
+        self._enable_chain()
+
+    def _resident_fits(self):
+        """Whether pack-resident mode can drop the live projections: every
+        shape packs (N % 32, K % 64, F % 16) and one layer's packs and the
+        LM head's pack each fit in 0.45 x free HBM (the build's peak growth
+        is one layer's packs; each dropped layer frees twice that).
+        Says why not, once, on stderr."""
+        import sys
+        l = self.layers[0]
+        mats = (l.wqkv, l.wo, l.wgate_up, l.wdown, self.lm_head)
+        why = None
+        if any(w.shape[0] % 32 or w.shape[1] % 64 for w in mats) \
+                or (l.wgate_up.shape[0] // 2) % 16:
+            why = "a projection's shape cannot be packed"
+        else:
+            torch.cuda.empty_cache()
+            free, _ = torch.cuda.mem_get_info(self.device)
+            layer = sum(w.numel() + 4 * w.shape[0] for w in mats[:4])
+            head = self.lm_head.numel() + 4 * self.lm_head.shape[0]
+            if max(layer, head) > free * 0.45:
+                why = "a layer's packs do not fit in free memory"
+        if why:
+            print(f"ollamamq_amd: OLLAMAMQ_FP8_RESIDENT ignored for "
+                  f"{self.cfg.name}: {why}; live weights kept",
+                  file=sys.stderr)
+        return why is None
+
+    def _pack_resident(self):
+        """Pack-resident build: pack one layer, drop that layer's live
+        matrices, go on; the LM head last.  The packs are then the weights
+        (the live ones equalled them exactly: requantising dequantised
+        values is exact and unpack_weight_fp8 inverts the pack).  embed,
+        biases and norm weights stay bf16.  head_dim != 128 models have no
+        fused chain and pack qkv in plain order."""
+        nl, nkl = self.n_local_heads, self.n_local_kv_heads
+        for l in self.layers:
+            if self.cfg.head_dim == 128:
+                l.wqkv_pk = ops.pack_weight_qkv_rope_fp8(l.wqkv, nl, nkl)
+                if l.bqkv is not None:
+                    l.bqkv_rp = ops.qkv_rope_bias_order(l.bqkv, nl, nkl)
+            else:
+                l.wqkv_pk = ops.pack_weight_fp8(l.wqkv)
+            l.wo_pk = ops.pack_weight_fp8(l.wo)
+            l.wgu_pk = ops.pack_weight_gu_fp8(l.wgate_up)
+            l.wdown_pk = ops.pack_weight_fp8(l.wdown)
+            l.wqkv = l.wo = l.wgate_up = l.wdown = None
+        self.lm_head_pk = ops.pack_weight_fp8(self.lm_head)
+        self.lm_head = None
+        torch.cuda.empty_cache()
+        if self.cfg.head_dim == 128:
+            # the generic path's qkv column map, uploaded before any graph
+            # capture can meet its first use
+            from ..ops import hip
+            hip.w8_colmap(nl, nkl, self.device)
+
+    def _enable_chain(self):
+        import os
         self.fused_chain = (
             self.tp_size == 1 and self.group is None
+            and self.cfg.head_dim == 128
             and os.environ.get("OLLAMAMQ_NO_CHAIN") != "1"
             and self.lm_head_pk is not None
             and all(l.wqkv_pk is not None and l.wo_pk is not None
@@ -418,14 +495,22 @@ class LlamaModel:
         return x
 
     def weight_bytes(self) -> int:
-        n = self.embed.numel() + self.lm_head.numel() + self.final_norm.numel()
+        """Bytes of the model's weights.  A matrix that pack-resident mode
+        dropped counts as its pack: one byte per element plus four per row
+        of scales."""
+        es = self.embed.element_size()
+
+        def mat(w, pk):
+            return w.numel() * es if w is not None else pk.nbytes()
+
+        n = (self.embed.numel() + self.final_norm.numel()) * es \
+            + mat(self.lm_head, self.lm_head_pk)
         for l in self.layers:
-            n += (
-                l.wqkv.numel() + l.wo.numel() + l.wgate_up.numel()
-                + l.wdown.numel() + l.attn_norm.numel() + l.mlp_norm.numel()
-                + (l.bqkv.numel() if l.bqkv is not None else 0)
-            )
-        return n * self.embed.element_size()
+            n += (mat(l.wqkv, l.wqkv_pk) + mat(l.wo, l.wo_pk)
+                  + mat(l.wgate_up, l.wgu_pk) + mat(l.wdown, l.wdown_pk))
+            n += (l.attn_norm.numel() + l.mlp_norm.numel()
+                  + (l.bqkv.numel() if l.bqkv is not None else 0)) * es
+        return n
 
     # -- forward -----------------------------------------------------------
     def forward(
@@ -451,8 +536,11 @@ class LlamaModel:
                 x, residual, layer.attn_norm, cfg.norm_eps
             )
             # NB: no packed= here — wqkv_pk has the norm weight folded in
-            # and is readable only by the fused chain
-            qkv = ops.linear(normed, layer.wqkv, layer.bqkv)
+            # and is readable only by the fused chain.  Pack-resident:
+            # wqkv is None and the W8 GEMM un-permutes the pair order.
+            qkv = ops.linear(normed, layer.wqkv, layer.bqkv,
+                             packed=layer.wqkv_pk if self.fp8_resident
+                             else None)
             nl, nkl, d = self.n_local_heads, self.n_local_kv_heads, cfg.head_dim
             q, k, v = qkv.split([nl * d, nkl * d, nkl * d], dim=-1)
             q = q.view(-1, nl, d)
@@ -485,7 +573,10 @@ class LlamaModel:
         # above 64 rows, prefill, or a model without the fused chain (which
         # covers decode up to 64 rows), and the direct-load MT2 streaming
         # GEMM loses to the library above batch 32 (doubled x scatter)
-        logits = ops.linear(h, self.lm_head)
+        # (pack-resident: lm_head is None and the pack is the weight)
+        logits = ops.linear(h, self.lm_head,
+                            packed=self.lm_head_pk if self.fp8_resident
+                            else None)
         if self.tp_size > 1:
             # vocab-parallel logits: all-gather shards on the last dim
             shards = [torch.empty_like(logits) for _ in range(self.tp_size)]
@@ -525,7 +616,7 @@ class LlamaModel:
             # fused rmsnorm -> qkv -> RoPE -> paged KV append: q comes
             # back rotated in standard layout, k/v land in the pool
             qkv = ops.qkv_rope_fused(
-                res, layer.wqkv_pk, layer.wqkv.shape[0], layer.bqkv_rp,
+                res, layer.wqkv_pk, (nl + 2 * nkl) * d, layer.bqkv_rp,
                 kv_cache, li, positions, slot_ids,
                 self.rope_cos, self.rope_sin, nl, nkl,
                 rstd=sq_a, rstd_nt=nt, inv_h=inv_h, eps=eps,
@@ -535,15 +626,15 @@ class LlamaModel:
             ops.linear_fused(attn, layer.wo_pk, H, res=res, sq_out=sq_b,
                              y=res, yfrag=1, K=nl * d, xlds=2, M_frag=B)
             act = ops.gu_fused(res, layer.wgu_pk,
-                               layer.wgate_up.shape[0], rstd=sq_b,
+                               2 * cfg.ffn, rstd=sq_b,
                                rstd_nt=tiles_h, inv_h=inv_h, eps=eps,
                                K=H, yfrag=1, M_frag=B)
             ops.linear_fused(act, layer.wdown_pk, H, res=res,
                              sq_out=sq_a, y=res, yfrag=1,
-                             K=layer.wdown.shape[1], xlds=2, M_frag=B)
+                             K=cfg.ffn, xlds=2, M_frag=B)
             nt = tiles_h
         logits = ops.linear_fused(res, self.lm_head_pk,
-                                  self.lm_head.shape[0], rstd=sq_a,
+                                  cfg.vocab, rstd=sq_a,
                                   rstd_nt=nt, inv_h=inv_h, eps=eps,
                                   K=H, xlds=2, M_frag=B)
         return logits[:B]

@@ -65,6 +65,7 @@ def _signatures():
                                i, i, i, i, vp],
         "sample_topk_bf16": [vp, vp, vp, vp, vp, vp, vp, i, i,
                              vp, vp, i, vp, vp, vp, vp],
+        "w8_gemm_bf16": [vp, vp, vp, vp, vp, vp, i, i, i, i64, i, vp],
     }
 
 
@@ -911,15 +912,98 @@ def wstream_pure(packed, N, K, ks):
     return sink
 
 
+def _streams(x, N):
+    """The generic dispatch's rule for the weight-streaming kernel."""
+    return USE_WSTREAM and x.shape[0] <= 64 \
+        and (N <= _WS_MAX_N or N >= 65536) \
+        and x.dtype == torch.bfloat16 and x.stride(1) == 1
+
+
 def linear(x, weight, bias=None, packed=None):
-    M, K = x.shape
     N = weight.shape[0]
-    if packed is not None and USE_WSTREAM and M <= 64 \
-            and (N <= _WS_MAX_N or N >= 65536) \
-            and x.dtype == torch.bfloat16 and x.stride(1) == 1:
+    if packed is not None and _streams(x, N):
         return linear_packed(x, packed, bias, N)
     # everything else (no pack, M > 64, N past _WS_MAX_N): library GEMM
     return torch.nn.functional.linear(x, weight, bias)
+
+
+# ---------------------------------------------------------------------------
+# W8A16 GEMM over an Fp8Pack for any M (csrc/kernels/w8_gemm.hip): what a
+# pack-resident fp8 model multiplies with wherever the streaming kernels do
+# not apply.
+
+W8_BM, W8_BN = 128, 128     # the kernel's block tile (w8_gemm.hip)
+_W8_MODES = {"plain": 0, "qkv": 1, "gu": 2}
+
+
+def w8_colmap(nl, nkl, device):
+    """int32 [N] natural column of each pack column of a ("qkv", nl, nkl)
+    pack, uploaded once per (nl, nkl, device)."""
+    return _cached(("w8_colmap", nl, nkl, str(device)),
+                   lambda: torch.tensor(qkv_rope_order(nl, nkl),
+                                        dtype=torch.int32, device=device))
+
+
+def linear_w8(x, pack, N, bias=None, out=None):
+    """y = x @ dq(W)^T (+ bias) with W an Fp8Pack of N rows, read as it is;
+    any M >= 1.  The pack's order picks the epilogue: plain columns, a
+    ("qkv", nl, nkl) pack un-permuted to natural columns (bias in natural
+    order), or a ("gu",) pack fused with SwiGLU, which returns
+    act[M, N // 2].  Allocates only the result (`out` to supply it)."""
+    if not isinstance(pack, Fp8Pack):
+        raise ValueError("linear_w8: pack must be an Fp8Pack")
+    if x.dim() != 2 or x.dtype != torch.bfloat16:
+        raise ValueError("linear_w8: x must be a 2-d bf16 tensor")
+    M, K = x.shape
+    if x.stride(1) != 1:
+        raise ValueError("linear_w8: x needs unit column stride")
+    if K % 64 or K < 64:
+        raise ValueError(f"linear_w8: K = {K} must be a multiple of 64")
+    if N % 32 or N < 32:
+        raise ValueError(f"linear_w8: N = {N} must be a multiple of 32")
+    if pack.scale.numel() != N or pack.codes.numel() != N * K:
+        raise ValueError("linear_w8: pack does not hold an "
+                         f"[{N}, {K}] matrix")
+    kind = pack.order[0]
+    if kind == "gu" and bias is not None:
+        raise ValueError("linear_w8: a gu pack takes no bias")
+    if bias is not None and (bias.dtype != torch.bfloat16
+                             or bias.numel() != N
+                             or not bias.is_contiguous()):
+        raise ValueError("linear_w8: bias must be contiguous bf16 [N]")
+    xs = x.stride(0) if M > 1 else K
+    if xs < K or xs % 8 or x.data_ptr() % 16:
+        raise ValueError("linear_w8: x rows must be 16-byte aligned and "
+                         "must not overlap")
+    shape = (M, N // 2 if kind == "gu" else N)
+    if out is None:
+        out = torch.empty(shape, dtype=x.dtype, device=x.device)
+    elif tuple(out.shape) != shape or out.dtype != x.dtype \
+            or not out.is_contiguous() or out.device != x.device \
+            or out.data_ptr() % 16:
+        raise ValueError(f"linear_w8: out must be contiguous bf16 "
+                         f"{shape} on x's device")
+    if M == 0:
+        return out
+    require()
+    colmap = w8_colmap(pack.order[1], pack.order[2], x.device) \
+        if kind == "qkv" else None
+    _check(_lib.w8_gemm_bf16(
+        _p(out), _p(x), _p(pack.codes), _p(pack.scale), _p(bias),
+        _p(colmap), M, N, K, xs, _W8_MODES[kind], _stream()), "w8_gemm")
+    return out
+
+
+def linear_resident(x, pack, bias=None):
+    """ops.linear with no live weight: a plain pack on a batch the generic
+    rule streams keeps the weight-streaming kernel; every other pack order
+    and batch goes to linear_w8."""
+    if not isinstance(pack, Fp8Pack):
+        raise ValueError("linear: weight=None needs packed= an Fp8Pack")
+    N = pack.scale.numel()
+    if pack.order[0] == "plain" and _streams(x, N):
+        return linear_packed(x, pack, bias, N)
+    return linear_w8(x, pack, N, bias)
 
 
 def swiglu(gate_up):

@@ -107,11 +107,33 @@ def linear(x, weight, bias=None, packed=None):
     """y = x @ weight.T (+ bias).  Library GEMM for prefill shapes; on the
     decode path (M<=64) a hand-written weight-streaming MFMA kernel runs
     over the pre-packed copy when `packed` is provided (hipBLASLt measured
-    1.8-4.6 TB/s vs the ~6.3 TB/s streaming roofline on these shapes)."""
+    1.8-4.6 TB/s vs the ~6.3 TB/s streaming roofline on these shapes).
+    weight=None with an Fp8Pack in `packed` multiplies by the pack itself
+    (pack-resident fp8 models; see _linear_resident)."""
+    if weight is None:
+        return _linear_resident(x, packed, bias)
     if _use_hip(x):
         from . import hip
         return hip.linear(x, weight, bias, packed)
     return torch.nn.functional.linear(x, weight, bias)
+
+
+def _linear_resident(x, pack, bias):
+    """linear with weight=None: `pack` (an ops.hip.Fp8Pack) IS the weight,
+    N = pack.scale.numel().  On the GPU a plain pack on a batch the generic
+    rule streams keeps linear_packed and everything else runs the W8A16 MFMA
+    GEMM (hip.linear_w8), which un-permutes a qkv pack and fuses SwiGLU into
+    a gu pack (the result is then act[M, N // 2]).  The reference path
+    multiplies by the unpacked dequantised matrix."""
+    from . import hip       # the pack helpers are pure torch
+    if not isinstance(pack, hip.Fp8Pack):
+        raise ValueError("linear: weight=None needs packed= an Fp8Pack")
+    if _use_hip(x):
+        return hip.linear_resident(x, pack, bias)
+    N = pack.scale.numel()
+    w = hip.unpack_weight_fp8(pack, N, x.shape[1]).to(x.dtype)
+    y = torch.nn.functional.linear(x, w, bias)
+    return ref.swiglu(y) if pack.order[0] == "gu" else y
 
 
 def pack_weight(w):
@@ -153,7 +175,11 @@ def gateup_swiglu(x, weight, packed_gu=None):
         from . import hip
         if hip.USE_WSTREAM and x.dtype == torch.bfloat16 \
                 and x.stride(1) == 1:
-            return hip.linear_gu(x, packed_gu, weight.shape[0])
+            N = weight.shape[0] if weight is not None \
+                else packed_gu.scale.numel()
+            return hip.linear_gu(x, packed_gu, N)
+    if weight is None:      # pack-resident: the gu pack fuses the SwiGLU
+        return linear(x, None, packed=packed_gu)
     return swiglu(linear(x, weight))
 
 

@@ -4,12 +4,20 @@ grid/addressing, loads only) that shows each geometry's load-path ceiling.
 
 Run on a GPU box: python tools/perf_gemm.py [M] [--sweep]
                   python tools/perf_gemm.py [M] --fp8 [--repeat R]
+                  python tools/perf_gemm.py --w8-prefill [--repeat R]
 
 --fp8: the same shapes, cold, with the fp8 (e4m3) pack next to the bf16
 pack of the same dequantised weights: the pure-stream ceiling of each
 geometry and the kernel through the direct (d1), LDS-staged (xl) and
 frag-input (fr, what the fused chain runs) activation paths; R repeats,
 printed as median (min..max) microseconds.
+
+--w8-prefill: the W8A16 MFMA GEMM over the fp8 pack (hip.linear_w8: qkv
+from the pair-ordered pack, gate_up from the GU pack with SwiGLU fused)
+against what a non-resident fp8 model runs, the library GEMM over the bf16
+dequantised weights (plus hip.swiglu for gate_up), at M = 128, 512, 2048;
+the two arms alternate R times, printed as median (min..max) and the ratio
+of the medians (library / w8: above 1 the new kernel is faster).
 
 COLD-weight protocol: cycles enough weight copies that the 256 MiB L3
 never serves a re-read (the serving loop streams weights from HBM once
@@ -86,8 +94,49 @@ def main_fp8(M, repeat):
         torch.cuda.empty_cache()
 
 
+def main_w8_prefill(repeat):
+    nl, nkl = 32, 8
+    for name, N, K in SHAPES:
+        order = {"qkv": ("qkv", nl, nkl), "gate_up": ("gu",)}.get(
+            name, ("plain",))
+        ncopy = max(2, (600 << 20) // (N * K) + 1)
+        p8, dq = [], []
+        for _ in range(ncopy):
+            w = (torch.randn(N, K, device="cuda") * K ** -0.5).bfloat16()
+            p8.append(hip._pack_fp8(w, order))
+            dq.append(hip.unpack_weight_fp8(p8[-1], N, K))
+            del w
+        for M in (128, 512, 2048):
+            x = torch.randn(M, K, device="cuda").bfloat16()
+            if order[0] == "gu":
+                lib = lambda w: hip.swiglu(torch.nn.functional.linear(x, w))
+            else:
+                lib = lambda w: torch.nn.functional.linear(x, w)
+            w8 = lambda p: hip.linear_w8(x, p, N)
+            got, want = w8(p8[0]).float(), lib(dq[0]).float()
+            err = float((got - want).abs().max() / want.abs().max())
+            t = {"lib": [], "w8": []}
+            for _ in range(repeat):         # alternate the two arms
+                t["lib"].append(bench(lib, dq, ncopy, n=20))
+                t["w8"].append(bench(w8, p8, ncopy, n=20))
+            line = f"{name:8s} N={N:6d} K={K:6d} M={M:5d}"
+            for tag in ("lib", "w8"):
+                ts = sorted(t[tag])
+                line += (f" | {tag} {ts[len(ts)//2]*1e6:8.1f}us "
+                         f"({ts[0]*1e6:.1f}..{ts[-1]*1e6:.1f})")
+            ratio = sorted(t["lib"])[repeat // 2] / sorted(t["w8"])[repeat // 2]
+            print(line + f" | lib/w8 {ratio:5.2f} | max rel diff {err:.1e}",
+                  flush=True)
+        del p8, dq
+        torch.cuda.empty_cache()
+
+
 def main():
     hip.require()
+    if "--w8-prefill" in sys.argv:
+        repeat = int(sys.argv[sys.argv.index("--repeat") + 1]) \
+            if "--repeat" in sys.argv else 3
+        return main_w8_prefill(repeat)
     M = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() \
         else 32
     sweep = "--sweep" in sys.argv
