@@ -59,7 +59,8 @@ _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 _KERNEL_FLAGS = {"topk_sample.hip": _NO_PK_F32,
                  "decode_attn_blk.hip": _NO_PK_F32,
                  "prefill_attn_kv8.hip": _NO_PK_F32,
-                 "w8_gemm.hip": _NO_PK_F32}
+                 "w8_gemm.hip": _NO_PK_F32,
+                 "w8a8_gemm.hip": _NO_PK_F32}
 
 
 def build_dispatcher(force=False):

@@ -268,6 +268,7 @@ class LlamaModel:
         process_group=None,
         fast_init: bool = False,
         fp8_resident: Optional[bool] = None,
+        fp8_act: Optional[bool] = None,
     ):
         assert cfg.n_heads % tp_size == 0, "n_heads must divide TP"
         self.cfg = cfg
@@ -334,6 +335,17 @@ class LlamaModel:
         self.lm_head_pk = None
         self.fused_chain = False
         self._pack_weights()
+        # fp8 activations on the generic path's GEMMs (None:
+        # OLLAMAMQ_FP8_ACT=1): W8A8 instead of W8A16 wherever the resident
+        # packs multiply through linear_w8.  Needs pack-resident mode.
+        if fp8_act is None:
+            import os
+            fp8_act = os.environ.get("OLLAMAMQ_FP8_ACT") == "1"
+        self.fp8_act = bool(fp8_act and self.fp8_resident)
+        if fp8_act and not self.fp8_act:
+            import sys
+            print(f"ollamamq_amd: OLLAMAMQ_FP8_ACT ignored for {cfg.name}: "
+                  "the model is not pack-resident fp8", file=sys.stderr)
 
     def _pack_weights(self):
         """Build MFMA-fragment-order packed copies of every projection for
@@ -540,7 +552,7 @@ class LlamaModel:
             # wqkv is None and the W8 GEMM un-permutes the pair order.
             qkv = ops.linear(normed, layer.wqkv, layer.bqkv,
                              packed=layer.wqkv_pk if self.fp8_resident
-                             else None)
+                             else None, act_fp8=self.fp8_act)
             nl, nkl, d = self.n_local_heads, self.n_local_kv_heads, cfg.head_dim
             q, k, v = qkv.split([nl * d, nkl * d, nkl * d], dim=-1)
             q = q.view(-1, nl, d)
@@ -550,14 +562,15 @@ class LlamaModel:
                             self.rope_cos, self.rope_sin)
             attn = ops.attention(q, kv_cache, li, attn_meta)
             x = ops.linear(attn.view(-1, nl * d), layer.wo,
-                           packed=layer.wo_pk)
+                           packed=layer.wo_pk, act_fp8=self.fp8_act)
             self._allreduce(x)  # RCCL all-reduce #1 (TP)
             normed, residual = ops.rmsnorm_residual(
                 x, residual, layer.mlp_norm, cfg.norm_eps
             )
             act = ops.gateup_swiglu(normed, layer.wgate_up,
-                                    layer.wgu_pk)
-            x = ops.linear(act, layer.wdown, packed=layer.wdown_pk)
+                                    layer.wgu_pk, act_fp8=self.fp8_act)
+            x = ops.linear(act, layer.wdown, packed=layer.wdown_pk,
+                           act_fp8=self.fp8_act)
             self._allreduce(x)  # RCCL all-reduce #2 (TP)
 
         # Only the last token of each sequence needs logits.
@@ -576,7 +589,7 @@ class LlamaModel:
         # (pack-resident: lm_head is None and the pack is the weight)
         logits = ops.linear(h, self.lm_head,
                             packed=self.lm_head_pk if self.fp8_resident
-                            else None)
+                            else None, act_fp8=self.fp8_act)
         if self.tp_size > 1:
             # vocab-parallel logits: all-gather shards on the last dim
             shards = [torch.empty_like(logits) for _ in range(self.tp_size)]

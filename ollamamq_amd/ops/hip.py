@@ -66,6 +66,8 @@ def _signatures():
         "sample_topk_bf16": [vp, vp, vp, vp, vp, vp, vp, i, i,
                              vp, vp, i, vp, vp, vp, vp],
         "w8_gemm_bf16": [vp, vp, vp, vp, vp, vp, i, i, i, i64, i, vp],
+        "act_quant_fp8": [vp, vp, vp, i, i, i64, vp],
+        "w8a8_gemm_bf16": [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, vp],
     }
 
 
@@ -944,36 +946,32 @@ def w8_colmap(nl, nkl, device):
                                         dtype=torch.int32, device=device))
 
 
-def linear_w8(x, pack, N, bias=None, out=None):
-    """y = x @ dq(W)^T (+ bias) with W an Fp8Pack of N rows, read as it is;
-    any M >= 1.  The pack's order picks the epilogue: plain columns, a
-    ("qkv", nl, nkl) pack un-permuted to natural columns (bias in natural
-    order), or a ("gu",) pack fused with SwiGLU, which returns
-    act[M, N // 2].  Allocates only the result (`out` to supply it)."""
+def _w8_args(op, x, pack, N, bias, out):
+    """The argument contract linear_w8 and linear_w8a8 share:
+    (M, K, x row stride, pack kind, result)."""
     if not isinstance(pack, Fp8Pack):
-        raise ValueError("linear_w8: pack must be an Fp8Pack")
+        raise ValueError(f"{op}: pack must be an Fp8Pack")
     if x.dim() != 2 or x.dtype != torch.bfloat16:
-        raise ValueError("linear_w8: x must be a 2-d bf16 tensor")
+        raise ValueError(f"{op}: x must be a 2-d bf16 tensor")
     M, K = x.shape
     if x.stride(1) != 1:
-        raise ValueError("linear_w8: x needs unit column stride")
+        raise ValueError(f"{op}: x needs unit column stride")
     if K % 64 or K < 64:
-        raise ValueError(f"linear_w8: K = {K} must be a multiple of 64")
+        raise ValueError(f"{op}: K = {K} must be a multiple of 64")
     if N % 32 or N < 32:
-        raise ValueError(f"linear_w8: N = {N} must be a multiple of 32")
+        raise ValueError(f"{op}: N = {N} must be a multiple of 32")
     if pack.scale.numel() != N or pack.codes.numel() != N * K:
-        raise ValueError("linear_w8: pack does not hold an "
-                         f"[{N}, {K}] matrix")
+        raise ValueError(f"{op}: pack does not hold an [{N}, {K}] matrix")
     kind = pack.order[0]
     if kind == "gu" and bias is not None:
-        raise ValueError("linear_w8: a gu pack takes no bias")
+        raise ValueError(f"{op}: a gu pack takes no bias")
     if bias is not None and (bias.dtype != torch.bfloat16
                              or bias.numel() != N
                              or not bias.is_contiguous()):
-        raise ValueError("linear_w8: bias must be contiguous bf16 [N]")
+        raise ValueError(f"{op}: bias must be contiguous bf16 [N]")
     xs = x.stride(0) if M > 1 else K
     if xs < K or xs % 8 or x.data_ptr() % 16:
-        raise ValueError("linear_w8: x rows must be 16-byte aligned and "
+        raise ValueError(f"{op}: x rows must be 16-byte aligned and "
                          "must not overlap")
     shape = (M, N // 2 if kind == "gu" else N)
     if out is None:
@@ -981,8 +979,18 @@ def linear_w8(x, pack, N, bias=None, out=None):
     elif tuple(out.shape) != shape or out.dtype != x.dtype \
             or not out.is_contiguous() or out.device != x.device \
             or out.data_ptr() % 16:
-        raise ValueError(f"linear_w8: out must be contiguous bf16 "
+        raise ValueError(f"{op}: out must be contiguous bf16 "
                          f"{shape} on x's device")
+    return M, K, xs, kind, out
+
+
+def linear_w8(x, pack, N, bias=None, out=None):
+    """y = x @ dq(W)^T (+ bias) with W an Fp8Pack of N rows, read as it is;
+    any M >= 1.  The pack's order picks the epilogue: plain columns, a
+    ("qkv", nl, nkl) pack un-permuted to natural columns (bias in natural
+    order), or a ("gu",) pack fused with SwiGLU, which returns
+    act[M, N // 2].  Allocates only the result (`out` to supply it)."""
+    M, K, xs, kind, out = _w8_args("linear_w8", x, pack, N, bias, out)
     if M == 0:
         return out
     require()
@@ -994,16 +1002,71 @@ def linear_w8(x, pack, N, bias=None, out=None):
     return out
 
 
-def linear_resident(x, pack, bias=None):
+# ---------------------------------------------------------------------------
+# W8A8 (csrc/kernels/w8a8_gemm.hip): activations quantised per row to e4m3
+# with a power-of-two scale, multiplied by the pack on the fp8 MFMA.
+
+def quantize_act_fp8(x, codes=None, exps=None):
+    """Per-row ops.quant.quantize_fp8 of a bf16 [M, K] activation (16-byte
+    aligned rows, unit column stride, K % 8 == 0) in one kernel:
+    (codes uint8 [M, K] dense, exps int32 [M]); x ~ dq(codes) * 2^exps."""
+    if x.dim() != 2 or x.dtype != torch.bfloat16 or x.stride(1) != 1:
+        raise ValueError("quantize_act_fp8: x must be 2-d bf16 with unit "
+                         "column stride")
+    M, K = x.shape
+    xs = x.stride(0) if M > 1 else K
+    if K % 8 or K < 8 or xs < K or xs % 8 or x.data_ptr() % 16:
+        raise ValueError("quantize_act_fp8: K must be a multiple of 8 and "
+                         "x rows 16-byte aligned")
+    if codes is None:
+        codes = torch.empty((M, K), dtype=torch.uint8, device=x.device)
+    elif tuple(codes.shape) != (M, K) or codes.dtype != torch.uint8 \
+            or not codes.is_contiguous() or codes.device != x.device \
+            or codes.data_ptr() % 16:
+        raise ValueError("quantize_act_fp8: codes must be contiguous uint8 "
+                         f"[{M}, {K}] on x's device")
+    if exps is None:
+        exps = torch.empty(M, dtype=torch.int32, device=x.device)
+    elif tuple(exps.shape) != (M,) or exps.dtype != torch.int32 \
+            or not exps.is_contiguous() or exps.device != x.device:
+        raise ValueError(f"quantize_act_fp8: exps must be int32 [{M}] on "
+                         "x's device")
+    if M == 0:
+        return codes, exps
+    require()
+    _check(_lib.act_quant_fp8(_p(codes), _p(exps), _p(x), M, K, xs,
+                              _stream()), "act_quant_fp8")
+    return codes, exps
+
+
+def linear_w8a8(x, pack, N, bias=None, out=None):
+    """linear_w8 with fp8 activations: x is quantised per row
+    (quantize_act_fp8) and y = dq(xq) @ dq(W)^T (+ bias) runs on the fp8
+    MFMA; same packs, epilogues and argument contract as linear_w8.
+    Allocates the result (`out` to supply it), the codes and the
+    exponents."""
+    M, K, xs, kind, out = _w8_args("linear_w8a8", x, pack, N, bias, out)
+    if M == 0:
+        return out
+    xq, xe = quantize_act_fp8(x)
+    colmap = w8_colmap(pack.order[1], pack.order[2], x.device) \
+        if kind == "qkv" else None
+    _check(_lib.w8a8_gemm_bf16(
+        _p(out), _p(xq), _p(xe), _p(pack.codes), _p(pack.scale), _p(bias),
+        _p(colmap), M, N, K, _W8_MODES[kind], _stream()), "w8a8_gemm")
+    return out
+
+
+def linear_resident(x, pack, bias=None, act_fp8=False):
     """ops.linear with no live weight: a plain pack on a batch the generic
     rule streams keeps the weight-streaming kernel; every other pack order
-    and batch goes to linear_w8."""
+    and batch goes to linear_w8, or to linear_w8a8 with act_fp8."""
     if not isinstance(pack, Fp8Pack):
         raise ValueError("linear: weight=None needs packed= an Fp8Pack")
     N = pack.scale.numel()
     if pack.order[0] == "plain" and _streams(x, N):
         return linear_packed(x, pack, bias, N)
-    return linear_w8(x, pack, N, bias)
+    return (linear_w8a8 if act_fp8 else linear_w8)(x, pack, N, bias)
 
 
 def swiglu(gate_up):

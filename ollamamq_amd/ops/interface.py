@@ -103,36 +103,40 @@ def attention(q, cache, layer, meta: AttnMeta):
     return ref.attention(q, cache, layer, meta)
 
 
-def linear(x, weight, bias=None, packed=None):
+def linear(x, weight, bias=None, packed=None, act_fp8=False):
     """y = x @ weight.T (+ bias).  Library GEMM for prefill shapes; on the
     decode path (M<=64) a hand-written weight-streaming MFMA kernel runs
     over the pre-packed copy when `packed` is provided (hipBLASLt measured
     1.8-4.6 TB/s vs the ~6.3 TB/s streaming roofline on these shapes).
     weight=None with an Fp8Pack in `packed` multiplies by the pack itself
-    (pack-resident fp8 models; see _linear_resident)."""
+    (pack-resident fp8 models; see _linear_resident); only there does
+    act_fp8 count: the W8A8 GEMM over per-row fp8 activations replaces the
+    W8A16 one."""
     if weight is None:
-        return _linear_resident(x, packed, bias)
+        return _linear_resident(x, packed, bias, act_fp8)
     if _use_hip(x):
         from . import hip
         return hip.linear(x, weight, bias, packed)
     return torch.nn.functional.linear(x, weight, bias)
 
 
-def _linear_resident(x, pack, bias):
+def _linear_resident(x, pack, bias, act_fp8=False):
     """linear with weight=None: `pack` (an ops.hip.Fp8Pack) IS the weight,
     N = pack.scale.numel().  On the GPU a plain pack on a batch the generic
     rule streams keeps linear_packed and everything else runs the W8A16 MFMA
     GEMM (hip.linear_w8), which un-permutes a qkv pack and fuses SwiGLU into
-    a gu pack (the result is then act[M, N // 2]).  The reference path
-    multiplies by the unpacked dequantised matrix."""
+    a gu pack (the result is then act[M, N // 2]); with act_fp8 that GEMM is
+    hip.linear_w8a8.  The reference path multiplies by the unpacked
+    dequantised matrix (ref.linear_w8a8 with act_fp8)."""
     from . import hip       # the pack helpers are pure torch
     if not isinstance(pack, hip.Fp8Pack):
         raise ValueError("linear: weight=None needs packed= an Fp8Pack")
     if _use_hip(x):
-        return hip.linear_resident(x, pack, bias)
+        return hip.linear_resident(x, pack, bias, act_fp8)
     N = pack.scale.numel()
     w = hip.unpack_weight_fp8(pack, N, x.shape[1]).to(x.dtype)
-    y = torch.nn.functional.linear(x, w, bias)
+    y = ref.linear_w8a8(x, w, bias) if act_fp8 \
+        else torch.nn.functional.linear(x, w, bias)
     return ref.swiglu(y) if pack.order[0] == "gu" else y
 
 
@@ -165,7 +169,7 @@ def swiglu(gate_up):
     return ref.swiglu(gate_up)
 
 
-def gateup_swiglu(x, weight, packed_gu=None):
+def gateup_swiglu(x, weight, packed_gu=None, act_fp8=False):
     """act = swiglu(x @ Wgu^T).  On the decode path (M<=32) with a
     GU-packed copy this is ONE fused weight-streaming kernel; otherwise
     the library GEMM + the swiglu kernel.  (An MT2 variant for 33..64
@@ -179,7 +183,7 @@ def gateup_swiglu(x, weight, packed_gu=None):
                 else packed_gu.scale.numel()
             return hip.linear_gu(x, packed_gu, N)
     if weight is None:      # pack-resident: the gu pack fuses the SwiGLU
-        return linear(x, None, packed=packed_gu)
+        return linear(x, None, packed=packed_gu, act_fp8=act_fp8)
     return swiglu(linear(x, weight))
 
 

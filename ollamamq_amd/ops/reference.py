@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import torch
 
-from .quant import kv_fp8_decode, kv_fp8_encode
+from .quant import kv_fp8_decode, kv_fp8_encode, quantize_fp8
 
 
 def rmsnorm_residual(x, residual, weight, eps):
@@ -118,6 +118,13 @@ def swiglu(gate_up):
     g = gate_up[..., :f].float()
     u = gate_up[..., f:].float()
     return (torch.nn.functional.silu(g) * u).to(gate_up.dtype)
+
+
+def linear_w8a8(x, w, bias=None):
+    """W8A8 linear: x [M, K] quantised per row to e4m3 with a power-of-two
+    scale (quant.quantize_fp8), then x_dq @ w.T (+ bias); w holds the
+    dequantised weight values."""
+    return torch.nn.functional.linear(quantize_fp8(x)[2], w, bias)
 
 
 def sample(logits, temperature, top_k, top_p, generator=None):

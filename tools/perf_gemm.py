@@ -15,9 +15,11 @@ printed as median (min..max) microseconds.
 --w8-prefill: the W8A16 MFMA GEMM over the fp8 pack (hip.linear_w8: qkv
 from the pair-ordered pack, gate_up from the GU pack with SwiGLU fused)
 against what a non-resident fp8 model runs, the library GEMM over the bf16
-dequantised weights (plus hip.swiglu for gate_up), at M = 128, 512, 2048;
-the two arms alternate R times, printed as median (min..max) and the ratio
-of the medians (library / w8: above 1 the new kernel is faster).
+dequantised weights (plus hip.swiglu for gate_up), at M = 128, 512, 2048,
+and the W8A8 GEMM (hip.linear_w8a8, activation quantiser included; "aq" is
+the quantiser alone); the arms alternate R times, printed as median
+(min..max) and the ratios of the medians (library / w8 and w8 / w8a8: above
+1 the kernel named second is faster).
 
 COLD-weight protocol: cycles enough weight copies that the 256 MiB L3
 never serves a re-read (the serving loop streams weights from HBM once
@@ -113,19 +115,29 @@ def main_w8_prefill(repeat):
             else:
                 lib = lambda w: torch.nn.functional.linear(x, w)
             w8 = lambda p: hip.linear_w8(x, p, N)
+            w8a8 = lambda p: hip.linear_w8a8(x, p, N)
+            aq = lambda p: hip.quantize_act_fp8(x)
             got, want = w8(p8[0]).float(), lib(dq[0]).float()
             err = float((got - want).abs().max() / want.abs().max())
-            t = {"lib": [], "w8": []}
-            for _ in range(repeat):         # alternate the two arms
+            err8 = float((w8a8(p8[0]).float() - want).abs().max()
+                         / want.abs().max())
+            t = {"lib": [], "w8": [], "w8a8": [], "aq": []}
+            for _ in range(repeat):         # alternate the arms
                 t["lib"].append(bench(lib, dq, ncopy, n=20))
                 t["w8"].append(bench(w8, p8, ncopy, n=20))
+                t["w8a8"].append(bench(w8a8, p8, ncopy, n=20))
+                t["aq"].append(bench(aq, p8, ncopy, n=20))
             line = f"{name:8s} N={N:6d} K={K:6d} M={M:5d}"
-            for tag in ("lib", "w8"):
+            med = {}
+            for tag in ("lib", "w8", "w8a8", "aq"):
                 ts = sorted(t[tag])
-                line += (f" | {tag} {ts[len(ts)//2]*1e6:8.1f}us "
+                med[tag] = ts[len(ts) // 2]
+                line += (f" | {tag} {med[tag]*1e6:8.1f}us "
                          f"({ts[0]*1e6:.1f}..{ts[-1]*1e6:.1f})")
-            ratio = sorted(t["lib"])[repeat // 2] / sorted(t["w8"])[repeat // 2]
-            print(line + f" | lib/w8 {ratio:5.2f} | max rel diff {err:.1e}",
+            print(line + f" | lib/w8 {med['lib'] / med['w8']:5.2f}"
+                  f" | w8/w8a8 {med['w8'] / med['w8a8']:5.2f}"
+                  f" | lib/w8a8 {med['lib'] / med['w8a8']:5.2f}"
+                  f" | max rel diff w8 {err:.1e} w8a8 {err8:.1e}",
                   flush=True)
         del p8, dq
         torch.cuda.empty_cache()
