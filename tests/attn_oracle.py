@@ -608,3 +608,173 @@ def assert_counting(got, truth, what=""):
     w = ratio(g, truth, per_vector=True)
     assert w <= 1.0, f"{what}: worst normalised error {w:.3f}"
     return w
+
+
+# ---------------------------------------------------------------------------
+# long contexts (tests/test_attention_long_gpu.py and
+# tests/test_attn_long_oracle_cpu.py): the same three tiers at serving lengths,
+# where a slot uses hundreds of page-table entries, a segment sweeps many
+# chunks and a window's lo_tok is thousands of keys from position 0.
+
+LONG_CTX = 8192
+LONG_DECODE_LENS = (511, 512, 513, 1023, 1024, 1025, 2047, 2049, 4095, 4096,
+                    8191, 8192)
+# (G, KVH): chunk 32 (G = 1) and chunk 64 (G = 4, and G = 8 with KVH = 1)
+LONG_GROUPS = ((1, 2), (4, 2), (8, 1))
+LONG_SPLITS = (None, 1, 2, 4, 8, 32)
+LONG_CAPTURE_LENS = (1, 70, 4096, 8192)
+LONG_WINDOWS = (1024, 4096)
+# 2 W + 1 keys at W = 4096 need one page more than LONG_CTX
+LONG_WINDOW_CTX = LONG_CTX + PAGE
+LONG_PREFILL_FRESH = ((512, 512), (1000, 1000), (1025, 1025))
+LONG_PREFILL_CONT = ((512, 4096), (33, 4097), (1, 8192))
+# 300 query rows at positions 3900..4199: at W = 4096 the window's lower
+# edge enters the sequence at row 196, at W = 1024 it sits 2877.. keys in
+LONG_PREFILL_WINDOW_CASE = (300, 4200)
+LONG_MIXED_DECODE = (2049, 8191)
+LONG_MIXED_PREFILL = ((512, 512), (512, 4096))
+LONG_REAL_LENS = (1025, 4096, 8191)
+LONG_REAL_PREFILL = ((1000, 1000), (512, 4096))
+LONG_PT_ENTRIES = (0, 32, 33, 255, 256, 511)
+# (window, key, blind row, seeing row) on the 300-row window chunk: the one
+# nonzero key is the first invisible key of the blind row (p + 1 of an
+# interior row; p - W of an interior row and of the last row, where the
+# W = 4096 edge is inside the sequence) and visible to the row beside it
+LONG_PREFILL_EDGE = ((0, 4051, 150, 151), (1024, 3026, 150, 149),
+                     (4096, 103, 299, 298))
+
+
+def long_window_lens(W):
+    """lo_tok = kv_len - W on 0, 1, just below a chunk edge, on it, just
+    past it, and W + 1 keys in."""
+    return (W, W + 1, W + 63, W + 64, W + 65, 2 * W + 1)
+
+
+def counting_kv_long(lens, KVH, pattern, extra=0):
+    """K = 0 and one-hot V for sequences of lens[i] (+ extra) keys.
+    pattern 0: V[j, h, d] = 1 where d == (j + 5 h + 3 i) % 128;
+    pattern 1: d == (j // 128 + 5 h + 3 i) % 128.  Together they give a
+    key's position modulo 16384."""
+    kvs = []
+    for i, n in enumerate(lens):
+        j = torch.arange(n + extra).unsqueeze(1)
+        if pattern:
+            j = j // D
+        hot = (j + 5 * torch.arange(KVH).unsqueeze(0) + 3 * i) % D
+        V = torch.zeros(n + extra, KVH, D).scatter_(
+            2, hot.unsqueeze(-1), 1.0).bfloat16()
+        kvs.append((torch.zeros(n + extra, KVH, D).bfloat16(), V))
+    return kvs
+
+
+def counting_long_ok(got, truth):
+    """[...] bool per 128-vector: |got - truth| <= 2^-8 |truth| (one fp32
+    division and one bf16 rounding of an exact count ratio) and exact zeros
+    where no visible key feeds the element."""
+    g, t = got.detach().double().cpu(), truth.detach().double().cpu()
+    assert g.shape == t.shape, f"shape {g.shape} vs {t.shape}"
+    ok = torch.isfinite(g) & ((g - t).abs() <= t.abs() * 2.0 ** -8)
+    return ok.all(dim=-1)
+
+
+def assert_counting_long(got, truth, what=""):
+    g = got.detach().cpu()
+    assert torch.isfinite(g).all(), f"{what}: non-finite output"
+    ok = counting_long_ok(g, truth)
+    assert bool(ok.all()), \
+        f"{what}: {int((~ok).sum())} of {ok.numel()} vectors off the count"
+
+
+# ---- single-target probes --------------------------------------------------
+# K = 0 except at target keys, which hold 32 x a +-1 code; q is the code of
+# the key it aims at.  The aimed key scores 4096 / sqrt(128) = 362, a zero
+# key 0 and another target key of the same sequence at most 362 - MIN_GAP
+# (probe_codes), so every other probability is exp(-110) = 0 in fp32 and
+# the output is V[t] bit for bit.  The negative sequences hold nothing but
+# their invisible keys, so their visible scores are all exactly 0.
+
+
+def long_probe_targets(n, window, CH, splits):
+    """Sorted visible targets of a decode row: the first and last key of
+    every segment under `splits`, kv_len - 1, lo_tok, and the first and
+    last position of page-table entries LONG_PT_ENTRIES."""
+    lo = n - window if (window > 0 and n > window) else 0
+    pos = {n - 1, lo}
+    for split in splits:
+        for c0, c1 in decode_segments(n, window, CH, split)[1]:
+            if c0 < c1:
+                pos.add(max(c0 * CH, lo))
+                pos.add(min(c1 * CH, n) - 1)
+    for e in LONG_PT_ENTRIES:
+        pos.update((e * PAGE, e * PAGE + PAGE - 1))
+    return sorted(t for t in pos if lo <= t < n)
+
+
+def long_probe_kv(n_keys, KVH, targets, seed):
+    """One sequence: K = 32 * code at `targets` (the i-th target carries
+    code i, in every kv head) and 0 elsewhere, V seeded with distinct
+    rows."""
+    h = probe_codes()
+    assert len(targets) <= N_CODES and len(set(targets)) == len(targets)
+    K = torch.zeros(n_keys, KVH, D)
+    if targets:
+        K[torch.tensor(targets)] = 32 * h[:len(targets)].unsqueeze(1)
+    V = rand_bf16_rows(n_keys, KVH, seed)
+    return K.bfloat16(), V
+
+
+def rand_bf16_rows(n, KVH, seed):
+    V = fo.rand_bf16(n, KVH, D, seed=seed)
+    flat = V.reshape(-1, D).float()
+    assert torch.unique(flat, dim=0).shape[0] == flat.shape[0]
+    return V
+
+
+def long_probe_rows(targets, Hq):
+    """Targets cut into whole rows of Hq (the tail repeats from the
+    start): [R, Hq] positions and [R, Hq] code numbers."""
+    idx = list(range(len(targets)))
+    while len(idx) % Hq:
+        idx.append(idx[len(idx) % len(targets)])
+    code = torch.tensor(idx).reshape(-1, Hq)
+    return torch.tensor(targets)[code], code
+
+
+def long_decode_probe_cases():
+    """(kv_len, window) of the decode probe sequences: lo_tok one past a
+    chunk edge at W = 1024 and on one at W = 4096."""
+    return [(513, 0), (2049, 0), (8192, 0), (1024 + 65, 1024),
+            (4096 + 64, 4096)]
+
+
+def long_prefill_probe_seq(ql, n, W, Hq, KVH, seed):
+    """One prefill probe sequence ((K, V), targets [ql, Hq], code numbers
+    [ql, Hq]): per row and head a target from the diagonal p, the window
+    edge lo, and both ends of the page-table entries of LONG_PT_ENTRIES
+    that the row sees."""
+    fixed = sorted({e * PAGE + o for e in LONG_PT_ENTRIES
+                    for o in (0, PAGE - 1)})
+    rows = []
+    for r in range(ql):
+        p = n - ql + r
+        lo = max(0, p - W + 1) if W > 0 else 0
+        cand = [p, lo] + [t for t in fixed if lo <= t <= p]
+        rows.append([cand[(3 * r + hd) % len(cand)] for hd in range(Hq)])
+    uniq = sorted({t for row in rows for t in row})
+    num = {t: i for i, t in enumerate(uniq)}
+    code = torch.tensor([[num[t] for t in row] for row in rows])
+    return long_probe_kv(n, KVH, uniq, seed), torch.tensor(rows), code
+
+
+def long_prefill_probe_cases():
+    """((q_len, kv_len, window) positive, negative)."""
+    wq, wn = LONG_PREFILL_WINDOW_CASE
+    win = [(wq, wn, W) for W in LONG_WINDOWS]
+    return ([(512, 512, 0)] + [(a, b, 0) for a, b in LONG_PREFILL_CONT]
+            + win, [(33, 4097, 0)] + win)
+
+
+def long_prefill_neg_keys(ql, n, W):
+    """Positions no row of the chunk sees: p + 1 of the last row and
+    p - W of the first."""
+    return [t for t in (n, n - ql - W if W else -1) if t >= 0]

@@ -61,7 +61,16 @@ MINIS = {
         head_dim=128, ffn=1216, vocab=1056, max_ctx=512, rope_theta=10000.0,
         qkv_bias=True),
 }
+# The long case only (LONG_CONFIGS): the Qwen-shaped mini with a 4096-token
+# context and a serving-size window, and its twin without the window.
+_LONG = dict(n_layers=3, hidden=704, n_heads=7, n_kv_heads=1, head_dim=128,
+             ffn=1216, vocab=1056, max_ctx=4096, rope_theta=10000.0,
+             qkv_bias=True)
+MINIS["qwen-long-swa"] = LlamaConfig(name="qwen-long-swa",
+                                     sliding_window=1024, **_LONG)
+MINIS["qwen-long"] = LlamaConfig(name="qwen-long", **_LONG)
 CONFIGS = ("tiny", "tiny-qwen", "tiny-swa", "mha-mini", "qwen-mini")
+LONG_CONFIGS = ("qwen-long-swa", "qwen-long")
 
 
 def config(name):
@@ -417,9 +426,9 @@ def owned_mask(kv, lens_by_slot):
     given lengths (ownership from kv._slot_pages)."""
     mask = torch.zeros(kv.n_pages, kv.page_size, dtype=torch.bool)
     for slot, n in lens_by_slot.items():
-        pages = kv._slot_pages[slot]
-        for p in range(n):
-            mask[pages[p // kv.page_size], p % kv.page_size] = True
+        pos = torch.arange(n)
+        pages = torch.tensor(kv._slot_pages[slot], dtype=torch.long)
+        mask[pages[pos // kv.page_size], pos % kv.page_size] = True
     return mask
 
 
@@ -472,12 +481,13 @@ class Rig:
     """A model, a scrambled cache and token sequences; drives
     LlamaModel.forward directly (no engine) and checks what it left."""
 
-    def __init__(self, model, seqs, device, seed=0, max_slots=80):
+    def __init__(self, model, seqs, device, seed=0, max_slots=80,
+                 max_ctx=MAX_CTX):
         cfg = model.cfg
         self.model, self.seqs, self.dev = model, seqs, device
         pages = sum((len(s) + PAGE - 1) // PAGE for s in seqs) + 5
         self.kv = PagedKVCache.for_model(
-            cfg, n_pages=pages, max_slots=max_slots, max_ctx=MAX_CTX,
+            cfg, n_pages=pages, max_slots=max_slots, max_ctx=max_ctx,
             device=device, dtype=torch.bfloat16)
         scramble(self.kv, seed)
         self.slots = [self.kv.alloc_slot() for _ in seqs]
@@ -589,3 +599,22 @@ def forward_cases():
     cases += [(f"decode{B}", tuple(c + 1 for c in decode_ctx(B)))
               for B in sorted(set(DECODE_B + EXACT_B))]
     return cases
+
+
+# ---------------------------------------------------------------------------
+# the long case (LONG_CONFIGS): one sequence prefilled to LONG_PROMPT tokens
+# in chunks of LONG_CHUNK (continued chunks at 512, 1024, 1536 and 2048),
+# then LONG_STEPS decode steps at B = 5 beside four short rows
+
+LONG_PROMPT = 2100
+LONG_CHUNK = 512
+LONG_STEPS = 3
+LONG_SHORT_CTX = (15, 16, 63, 65)
+LONG_LENS = tuple(c + LONG_STEPS for c in (LONG_PROMPT,) + LONG_SHORT_CTX)
+LONG_MAX_CTX = 4096
+
+
+def long_chunks():
+    """[(start, end)] of the long prompt's prefill chunks."""
+    return [(a, min(a + LONG_CHUNK, LONG_PROMPT))
+            for a in range(0, LONG_PROMPT, LONG_CHUNK)]

@@ -57,6 +57,24 @@ def test_second_emulation_inside_budgets(name):
     assert worst <= 1.0
 
 
+@pytest.mark.parametrize("name", mo.LONG_CONFIGS)
+def test_second_emulation_long_case(name):
+    """The long case (2100-token prompt + 3 decode tokens beside four short
+    rows, window 1024 and none): the same emulation at 0.5 or less of every
+    budget derived at that length.  V of layer 0 is one bf16 rounding of the
+    same fp32 value in both runs, so its ratio is 1 / FACTOR by
+    construction."""
+    seqs, truth, budget = mo.truth_of(name, "long", mo.LONG_LENS)
+    assert len(seqs[0]) == mo.LONG_PROMPT + mo.LONG_STEPS
+    assert [a for a, _ in mo.long_chunks()][1:] == [512, 1024, 1536, 2048]
+    r = budget.fresh().hold_obs(mo.emulate_chain(mo.cpu_model(name), seqs),
+                                truth, f"{name} long")
+    lim = budget.lim["logits"]
+    print(f"second emulation {name} long: worst ratio {max(r.values()):.3f}"
+          f" (logits budget rel {lim[0]:.4f} mx {lim[1]:.4f})")
+    assert max(r.values()) <= 0.5, r
+
+
 def test_reference_budget_size():
     """The budgets are of the size the method assumes: logits rel of the
     reference run ~1e-2, far below the O(1) a wiring fault causes."""
